@@ -17,6 +17,10 @@ first-fit loops visit), ms_per_step = step wall time = proposal 
 (one host thread + HIP stream per session, GoalOptimizer's precompute pool); proposal_wall_s is then the mean
 per-proposal latency.
 
+A plain run sets up, runs the --warmup proposals, times the --steps proposals and prints the result line; "parity",
+"roofline" and "cpu_baseline" are null in it. --dump-outputs DIR also writes what the last timed proposal returned
+(dump_outputs()). Everything below is measured or checked only with --full, outside the timed region.
+
 Parity: the first timed proposal is checked against the committed oracle golden of the workload (tests/golden/:
 action log, final assignment and leaders, per-goal results, every goal's stats within 1e-9) -> "parity".
 
@@ -86,6 +90,7 @@ WORKLOAD_OPTIONS = {"c3": lambda: ccmi.OptimizationOptions(requested_destination
 WORKLOAD_GOLDEN = {"c1": "c1", "c2": "c2_default", "c2_c1goals": "c2_c1goals", "c3": "c3_default", "c4": "c4"}
 BYTES_PER_CANDIDATE = 96
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E (MI355X_MICROARCH.md)
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs writes at most this much array data
 # candidate-heavy C2 goal the CPU baseline samples on the box (the reference's costliest goal at C2)
 C2_SAMPLE_GOAL = "CpuUsageDistributionGoal"
 
@@ -329,8 +334,14 @@ def main() -> None:
                          "devices 0..N-1 of this process, one host thread each (independent what-if proposals)")
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-launch-pass", action="store_true", help="skip the instrumented scan-server-off proposal")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the instrumented warmup and scan-server-off proposals "
+                         "(roofline), the parity check against the committed golden, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed proposal returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-launch-pass", action="store_true",
+                    help="--full: skip the instrumented scan-server-off proposal")
     ap.add_argument("--cpu-sample-seconds", type=float, default=25.0)
     ap.add_argument("--what-if-procs", type=int, default=16)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2")
@@ -346,6 +357,8 @@ def main() -> None:
                          "instead of one independent what-if proposal per rank")
     ap.add_argument("--lib", default=None, help=argparse.SUPPRESS)  # tests: the CPU emulation build (tests/emu)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -415,26 +428,30 @@ def main() -> None:
                 torch.cuda.synchronize(d)
 
     from concurrent.futures import ThreadPoolExecutor
-    # Warmup proposals double as the instrumented pass: HIP events around every launched scan kernel and the scan
-    # server's in-kernel busy time per command (outside the timed region). Every local device warms up (its first
-    # launches load the code object); device 0's session is the instrumented one.
+    # Every local device warms up (its first launches load the code object). With --full the warmup proposals double
+    # as the instrumented pass: HIP events around every launched scan kernel and the scan server's in-kernel busy time
+    # per command (outside the timed region), on device 0's session; the roofline needs one, so at least one runs.
     inst_perf = inst_cands = None
-    for w in range(max(1, args.warmup)):
+    n_warmup = max(1, args.warmup) if args.full else args.warmup
+    for w in range(n_warmup):
         wss = [session(d) for d in local_devices]
-        wss[0].set_kernel_timing(True)
-        wss[0].reset_perf()
+        if args.full:
+            wss[0].set_kernel_timing(True)
+            wss[0].reset_perf()
         if len(wss) == 1:
             rs = [optimize(opt, wss[0], goals, options)]
         else:
             with ThreadPoolExecutor(len(wss)) as wp:
                 rs = list(wp.map(lambda s: optimize(opt, s, goals, options), wss))
-        inst_perf, inst_cands = wss[0].perf(), rs[0].candidates
+        if args.full:
+            inst_perf, inst_cands = wss[0].perf(), rs[0].candidates
         del wss
-        progress(f"warmup {w + 1}/{max(1, args.warmup)}: {rs[0].seconds:.2f} s")
+        progress(f"warmup {w + 1}/{n_warmup}: {rs[0].seconds:.2f} s")
     # One more instrumented proposal with the scan server off (a launch per scan): the per-launch kernel times the
     # rocprofv3 trace of the same path can be checked against (rank 0, single GPU, outside the timed region).
     launch_perf = None
-    if world == 1 and len(local_devices) == 1 and not args.no_launch_pass and args.workload != "c4" and not group_mode:
+    if (args.full and world == 1 and len(local_devices) == 1 and not args.no_launch_pass and args.workload != "c4"
+            and not group_mode):
         os.environ["CCMI_SERVER"] = "0"
         try:
             ls = session()
@@ -498,8 +515,64 @@ def main() -> None:
         if sharded:  # every rank made the same decisions: one proposal's candidates per step
             cands = float(sum(r.candidates for r in results))
 
-    perf = inst_perf
-    intra = args.workload == "c4"  # JBOD: the dominant kernel is K6 (intra_brokers)
+    if rank != 0:
+        dist.destroy_process_group()
+        return
+    first = results[0]
+    line = {
+        "metric": "candidate moves evaluated/s + proposal wall time, 10K brokers/1M replicas",
+        "value": cands / elapsed,
+        "unit": "candidate moves evaluated/s",
+        "n_gpus": n_group if group_mode else world if world > 1 else len(local_devices),
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed * 1e3 / args.steps,
+        "higher_is_better": True,
+        "scaling": "strong" if sharded else "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (RandomCluster restatement, TestConstants seeds)",
+        "config": {"workload": workload_name,
+                   "brokers": buf.desc.num_brokers, "replicas": buf.desc.num_replicas,
+                   "partitions": buf.desc.num_partitions, "topics": buf.desc.num_topics,
+                   "goals": goal_names, "parallelism": (f"destination-sharded x{n_group} (one process, shard group: the scan servers MIN-combine "
+                                   f"each scan on the device)" if group_mode and sharded else
+                                   f"destination-sharded x{world} ({args.combiner} MIN combine per scan)" if sharded
+                                   else f"independent what-if per GPU x{max(world, len(local_devices))}"
+                                   + ("" if world > 1 or len(local_devices) == 1 else
+                                      " (one process, one host thread per device)"))},
+        "parity": check_parity(args.workload, sessions[0][0][0], first) if args.full else None,
+        "requests_per_gpu": S,
+        "devices": (sorted(set(local_devices)) if world == 1 and not group_mode else None),
+        "devices_note": (None if world > 1 or group_mode or len(set(local_devices)) == len(local_devices) else
+                         f"{len(local_devices)} sessions on {len(set(local_devices))} device(s): fewer GPUs than "
+                         f"--gpus on this box, so sessions share devices round-robin (a rehearsal, not a scaling point)"),
+        "proposal_wall_s": sum(r.seconds for r in results) / len(results),
+        "session_upload_s": upload_s,
+        "timed_region": "GoalOptimizer.optimizations on sessions already resident in HBM (upload excluded)",
+        "candidates_per_step": first.candidates,
+        "actions_per_step": len(first.actions),
+        "proposals_per_step": len(first.proposals),
+        "per_goal_gpu_s": {g.name: round(g.seconds, 4) for g in first.goal_results},
+        "roofline": (roofline(args.workload, inst_perf, inst_cands, launch_perf, elapsed / args.steps)
+                     if args.full else None),
+        "cpu_baseline": None,
+    }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sessions[0][-1][0], per_device[0][-S], args.workload == "c4")
+    if args.full and world == 1 and len(local_devices) == 1 and not args.no_cpu_baseline:
+        progress("cpu baseline")
+        line["cpu_baseline"] = cpu_baseline(lib, buf, args.workload, goal_names, options, first, device,
+                                            args.cpu_sample_seconds, args.what_if_procs)
+    print(json.dumps(line))
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def roofline(workload: str, perf, inst_cands, launch_perf, step_s: float) -> dict:
+    """The roofline entry of the result line (--full) from the instrumented warmup proposal's counters `perf`, the
+    scan-server-off proposal's `launch_perf` (None when it did not run) and the timed step's wall time."""
+    intra = workload == "c4"  # JBOD: the dominant kernel is K6 (intra_brokers)
     if intra:
         launches = max(1, perf.intra_launches)
         scan_avg_ms = perf.intra_kernel_ms / launches
@@ -531,112 +604,104 @@ def main() -> None:
             required_bytes_per_launch = perf.server_required * BYTES_PER_CANDIDATE / launches
             achieved = required_bytes_per_launch / (scan_avg_ms * 1e-3) / 1e9
 
-    if rank != 0:
-        dist.destroy_process_group()
-        return
-    first = results[0]
-    parity = check_parity(args.workload, sessions[0][0][0], first)
-    traffic, traffic_src = pmc_traffic(args.workload, INTRA_KERNELS if intra else SCAN_KERNELS)
+    traffic, traffic_src = pmc_traffic(workload, INTRA_KERNELS if intra else SCAN_KERNELS)
     traffic_unit = "HBM bytes per scan launch"
     if server:
-        st, ss = pmc_server_traffic(args.workload, perf)
+        st, ss = pmc_server_traffic(workload, perf)
         if per_command is not None:
             per_command["traffic"] = st
             per_command["traffic_over_algorithmic"] = st / per_command["algorithmic_bytes"] if st else None
-        traffic, traffic_src = pmc_traffic(args.workload, ("scan_server",))
+        traffic, traffic_src = pmc_traffic(workload, ("scan_server",))
         traffic_unit = "HBM bytes per scan_server launch"
-    line = {
-        "metric": "candidate moves evaluated/s + proposal wall time, 10K brokers/1M replicas",
-        "value": cands / elapsed,
-        "unit": "candidate moves evaluated/s",
-        "n_gpus": n_group if group_mode else world if world > 1 else len(local_devices),
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed * 1e3 / args.steps,
-        "higher_is_better": True,
-        "scaling": "strong" if sharded else "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (RandomCluster restatement, TestConstants seeds)",
-        "config": {"workload": workload_name,
-                   "brokers": buf.desc.num_brokers, "replicas": buf.desc.num_replicas,
-                   "partitions": buf.desc.num_partitions, "topics": buf.desc.num_topics,
-                   "goals": goal_names, "parallelism": (f"destination-sharded x{n_group} (one process, shard group: the scan servers MIN-combine "
-                                   f"each scan on the device)" if group_mode and sharded else
-                                   f"destination-sharded x{world} ({args.combiner} MIN combine per scan)" if sharded
-                                   else f"independent what-if per GPU x{max(world, len(local_devices))}"
-                                   + ("" if world > 1 or len(local_devices) == 1 else
-                                      " (one process, one host thread per device)"))},
-        "parity": parity,
-        "requests_per_gpu": S,
-        "devices": (sorted(set(local_devices)) if world == 1 and not group_mode else None),
-        "devices_note": (None if world > 1 or group_mode or len(set(local_devices)) == len(local_devices) else
-                         f"{len(local_devices)} sessions on {len(set(local_devices))} device(s): fewer GPUs than "
-                         f"--gpus on this box, so sessions share devices round-robin (a rehearsal, not a scaling point)"),
-        "proposal_wall_s": sum(r.seconds for r in results) / len(results),
-        "session_upload_s": upload_s,
-        "timed_region": "GoalOptimizer.optimizations on sessions already resident in HBM (upload excluded)",
-        "candidates_per_step": first.candidates,
-        "actions_per_step": len(first.actions),
-        "proposals_per_step": len(first.proposals),
-        "per_goal_gpu_s": {g.name: round(g.seconds, 4) for g in first.goal_results},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_unit": traffic_unit,
-                     "traffic_source": traffic_src,
-                     "kernel": ("K6 intra_brokers (one wavefront per broker; algorithmic bytes = 17 B per disk + 29 B per "
-                                "replica entry read once)" if intra else
-                                "K8 scan_server (persistent; per launch: the required candidates of its commands x 96 B "
-                                "over the launch's residency, HIP events on the session stream)" if server else
-                                "candidate scans (scan_cross/scan_pairs/scan_swap/chain_pairs/chain_rack_rows)"),
-                     "avg_launch_us": scan_avg_ms * 1e3,
-                     "avg_unit": "per launch",
-                     "per_command": per_command,
-                     "launches_per_step": perf.intra_launches if intra else perf.scan_launches,
-                     "server_launches_per_step": perf.server_launches,
-                     "server_commands_per_step": perf.server_scans,
-                     # the rocprof-derivable view of the same kernel: algorithmic bytes per scan_server launch over its
-                     # residency per launch (HIP events from launch to exit, idle polling included) — what a
-                     # rocprofv3 kernel trace's average scan_server duration gives
-                     "resident": None if not server or perf.server_resident_ms <= 0 else {
-                         "avg_launch_us": perf.server_resident_ms * 1e3 / max(1, perf.server_launches),
-                         "algorithmic_bytes_per_launch": perf.server_required * BYTES_PER_CANDIDATE
-                         / max(1, perf.server_launches),
-                         "achieved": perf.server_required * BYTES_PER_CANDIDATE / (perf.server_resident_ms * 1e-3) / 1e9,
-                         "frac": perf.server_required * BYTES_PER_CANDIDATE / (perf.server_resident_ms * 1e-3) / 1e9
-                         / HBM_PEAK_GBS,
-                         "busy_share": perf.server_busy_ms / perf.server_resident_ms},
-                     "server_payload_bytes_per_step": perf.server_payload_bytes,
-                     "device_evaluated_candidates_per_s": perf.scan_required / (elapsed / args.steps),
-                     "chain_launches_per_step": perf.chain_launches,
-                     "algorithmic_bytes_per_launch": required_bytes_per_launch,
-                     "traffic_over_algorithmic": (traffic / required_bytes_per_launch
-                                                  if traffic and required_bytes_per_launch else None),
-                     "required_candidates_per_step": perf.scan_required,
-                     "reference_equivalent_candidates_per_step": inst_cands,
-                     "stats_avg_launch_us": perf.stats_kernel_ms * 1e3 / max(1, perf.stats_launches),
-                     "stats_bytes_per_launch": perf.stats_bytes / max(1, perf.stats_launches),
-                     "host_syncs_per_step": perf.host_syncs,
-                     "intra_sort": None if not intra else {
-                         "launches_per_step": perf.intra_sort_launches,
-                         "avg_launch_us": perf.intra_sort_ms * 1e3 / max(1, perf.intra_sort_launches),
-                         "note": "K6's per-call entry sort, timed apart from intra_brokers (HIP events)"},
-                     "scan_cross": scan_cross_line(launch_perf or perf, args.workload),
-                     "launch_path": None if launch_perf is None else {
-                         "scan_launches": launch_perf.scan_launches,
-                         "avg_scan_launch_us": launch_perf.scan_kernel_ms * 1e3 / max(1, launch_perf.scan_launches),
-                         "achieved_gbs": (launch_perf.scan_required * BYTES_PER_CANDIDATE / max(1, launch_perf.scan_launches))
-                                         / max(1e-12, launch_perf.scan_kernel_ms * 1e-3 / max(1, launch_perf.scan_launches)) / 1e9,
-                         "note": "the same proposal with CCMI_SERVER=0 (one launch per scan), HIP events per launch"}},
-        "cpu_baseline": None,
-    }
-    if world == 1 and len(local_devices) == 1 and not args.no_cpu_baseline:
-        progress("cpu baseline")
-        line["cpu_baseline"] = cpu_baseline(lib, buf, args.workload, goal_names, options, first, device,
-                                            args.cpu_sample_seconds, args.what_if_procs)
-    print(json.dumps(line))
-    if world > 1:
-        dist.destroy_process_group()
+    return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_unit": traffic_unit,
+            "traffic_source": traffic_src,
+            "kernel": ("K6 intra_brokers (one wavefront per broker; algorithmic bytes = 17 B per disk + 29 B per "
+                       "replica entry read once)" if intra else
+                       "K8 scan_server (persistent; per launch: the required candidates of its commands x 96 B "
+                       "over the launch's residency, HIP events on the session stream)" if server else
+                       "candidate scans (scan_cross/scan_pairs/scan_swap/chain_pairs/chain_rack_rows)"),
+            "avg_launch_us": scan_avg_ms * 1e3,
+            "avg_unit": "per launch",
+            "per_command": per_command,
+            "launches_per_step": perf.intra_launches if intra else perf.scan_launches,
+            "server_launches_per_step": perf.server_launches,
+            "server_commands_per_step": perf.server_scans,
+            # the rocprof-derivable view of the same kernel: algorithmic bytes per scan_server launch over its
+            # residency per launch (HIP events from launch to exit, idle polling included) — what a
+            # rocprofv3 kernel trace's average scan_server duration gives
+            "resident": None if not server or perf.server_resident_ms <= 0 else {
+                "avg_launch_us": perf.server_resident_ms * 1e3 / max(1, perf.server_launches),
+                "algorithmic_bytes_per_launch": perf.server_required * BYTES_PER_CANDIDATE
+                / max(1, perf.server_launches),
+                "achieved": perf.server_required * BYTES_PER_CANDIDATE / (perf.server_resident_ms * 1e-3) / 1e9,
+                "frac": perf.server_required * BYTES_PER_CANDIDATE / (perf.server_resident_ms * 1e-3) / 1e9
+                / HBM_PEAK_GBS,
+                "busy_share": perf.server_busy_ms / perf.server_resident_ms},
+            "server_payload_bytes_per_step": perf.server_payload_bytes,
+            "device_evaluated_candidates_per_s": perf.scan_required / step_s,
+            "chain_launches_per_step": perf.chain_launches,
+            "algorithmic_bytes_per_launch": required_bytes_per_launch,
+            "traffic_over_algorithmic": (traffic / required_bytes_per_launch
+                                         if traffic and required_bytes_per_launch else None),
+            "required_candidates_per_step": perf.scan_required,
+            "reference_equivalent_candidates_per_step": inst_cands,
+            "stats_avg_launch_us": perf.stats_kernel_ms * 1e3 / max(1, perf.stats_launches),
+            "stats_bytes_per_launch": perf.stats_bytes / max(1, perf.stats_launches),
+            "host_syncs_per_step": perf.host_syncs,
+            "intra_sort": None if not intra else {
+                "launches_per_step": perf.intra_sort_launches,
+                "avg_launch_us": perf.intra_sort_ms * 1e3 / max(1, perf.intra_sort_launches),
+                "note": "K6's per-call entry sort, timed apart from intra_brokers (HIP events)"},
+            "scan_cross": scan_cross_line(launch_perf or perf, workload),
+            "launch_path": None if launch_perf is None else {
+                "scan_launches": launch_perf.scan_launches,
+                "avg_scan_launch_us": launch_perf.scan_kernel_ms * 1e3 / max(1, launch_perf.scan_launches),
+                "achieved_gbs": (launch_perf.scan_required * BYTES_PER_CANDIDATE / max(1, launch_perf.scan_launches))
+                                / max(1e-12, launch_perf.scan_kernel_ms * 1e-3 / max(1, launch_perf.scan_launches)) / 1e9,
+                "note": "the same proposal with CCMI_SERVER=0 (one launch per scan), HIP events per launch"}}
 
+
+def dump_outputs(out_dir: str, cm, result, jbod: bool) -> None:
+    """--dump-outputs: what the caller of the last timed GoalOptimizer.optimizations received, one float64 .npy per
+    array (every value is an integer below 2^53 or a double, so nothing is rounded): the ordered action log, the final
+    replica and leader placement, the ExecutionProposals (rows padded with -1 to 8 replicas) and, per goal, its outcome
+    and ClusterModelStats. Wall times are left out: two runs of one build write identical files. Above the byte cap
+    the row arrays keep a fixed seeded sample of their rows."""
+    import numpy as np
+    max_rf = 8
+    pad = lambda xs: list(xs) + [-1] * (max_rf - len(xs))  # noqa: E731
+    props = [[p.partition, p.partition_size, p.old_leader] + pad(p.old_replicas) + pad(p.new_replicas)
+             + (pad(p.old_disks) + pad(p.new_disks) if jbod else []) for p in result.proposals]
+    stats = []
+    for g in result.goal_results:
+        row = []
+        for v in g.stats.values():
+            row.extend(v if isinstance(v, list) else [v])
+        stats.append(row)
+    arrays = {
+        "actions": np.array(result.actions, dtype=np.float64).reshape(-1, 7),
+        "replica_distribution": np.array(cm.replica_distribution(), dtype=np.float64),
+        "leader_distribution": np.array(cm.leader_distribution(), dtype=np.float64),
+        "proposals": np.array(props, dtype=np.float64).reshape(-1, 3 + (4 if jbod else 2) * max_rf),
+        "goal_results": np.array([[g.succeeded, g.has_diff, g.candidates, g.actions] for g in result.goal_results],
+                                 dtype=np.float64),
+        "goal_stats": np.array(stats, dtype=np.float64),
+    }
+    if jbod:
+        arrays["replica_disks"] = np.array(cm.replica_disks(), dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        rng = np.random.default_rng(0)
+        for k, a in arrays.items():
+            keep = int(len(a) * DUMP_MAX_BYTES / total)
+            if 0 < keep < len(a):
+                arrays[k] = a[np.sort(rng.choice(len(a), keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    progress(f"outputs of the last timed proposal written to {out_dir} "
+             f"({sum(a.nbytes for a in arrays.values()) / 1e6:.1f} MB)")
 
 
 

@@ -105,6 +105,34 @@ def test_bench_plain_launch_runs_one_session_per_device(emu_lib):
     assert two["scaling"] == "weak" and "x2" in two["config"]["parallelism"]
 
 
+def test_bench_plain_run_is_lean_and_full_adds_the_rest(emu_lib):
+    """A plain run reports the headline figure only; --full adds the parity, roofline and (unless switched off) CPU
+    baseline entries without touching what the headline fields say."""
+    plain = _bench_emu(emu_lib, 1, 1, ("--steps", "2"))
+    full = _bench_emu(emu_lib, 1, 1, ("--steps", "2", "--full"))
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0
+    assert plain["parity"] is None and plain["roofline"] is None and plain["cpu_baseline"] is None
+    assert full["parity"] is not None and full["roofline"]["launches_per_step"] > 0 and full["cpu_baseline"] is None
+    for k in ("metric", "unit", "higher_is_better", "dtype", "candidates_per_step", "actions_per_step"):
+        assert plain[k] == full[k]
+    assert plain["value"] * plain["ms_per_step"] == pytest.approx(full["value"] * full["ms_per_step"], rel=1e-9)
+
+
+def test_bench_dump_outputs_repeat_exactly(emu_lib, tmp_path):
+    """--dump-outputs writes the last timed proposal as float64 arrays, identical from run to run."""
+    import numpy as np
+    lines = [_bench_emu(emu_lib, 1, 1, ("--dump-outputs", str(tmp_path / d))) for d in ("a", "b")]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "actions.npy" in names and "goal_stats.npy" in names
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64 and a.size > 0 and np.array_equal(a, b), n
+    assert np.load(tmp_path / "a" / "actions.npy").shape == (lines[0]["actions_per_step"], 7)
+    assert np.load(tmp_path / "a" / "proposals.npy").shape[0] == lines[0]["proposals_per_step"]
+    assert len(np.load(tmp_path / "a" / "goal_results.npy")) == len(lines[0]["config"]["goals"])
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 * 1000 * 1000
+
+
 def test_bench_plain_launch_with_fewer_devices_says_so(emu_lib):
     """--gpus 2 on a one-device box: both sessions on ordinal 0, reported as a rehearsal."""
     two = _bench_emu(emu_lib, 2, 1)

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 W=/tmp/ccmi_icache
 rm -rf "$W"
 timeout -s KILL 400 rocprofv3 --pmc ${COUNTERS:-SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH} \
-  --output-format csv -d "$W" -o ic -- python3 bench.py --workload c2 --no-cpu-baseline --no-launch-pass --steps 1 \
+  --output-format csv -d "$W" -o ic -- python3 bench.py --full --workload c2 --no-cpu-baseline --no-launch-pass --steps 1 \
   --warmup 0 > "$DST/icache_bench.json"
 python3 - "$W" > "$DST/icache_summary.json" <<'EOF'
 import csv, glob, json, sys

@@ -8,11 +8,11 @@ DST=gpurun_out/$OUT
 mkdir -p "$DST"
 export TMPDIR=/tmp
 for T in "$@"; do
-  CCMI_XCD_SLICE_MIN_COLS=$T timeout -k 10 300 python3 bench.py --workload c2 --no-cpu-baseline --steps 1 --warmup 1 \
+  CCMI_XCD_SLICE_MIN_COLS=$T timeout -k 10 300 python3 bench.py --full --workload c2 --no-cpu-baseline --steps 1 --warmup 1 \
     > "$DST/bench_$T.json"
   rm -rf /tmp/sweep_$T
   CCMI_XCD_SLICE_MIN_COLS=$T timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex scan_cross \
-    --output-format csv -d /tmp/sweep_$T -o s -- python3 bench.py --workload c2 --no-cpu-baseline --steps 1 --warmup 0 \
+    --output-format csv -d /tmp/sweep_$T -o s -- python3 bench.py --full --workload c2 --no-cpu-baseline --steps 1 --warmup 0 \
     > /dev/null
   python3 - "$T" "$DST" <<'PY'
 import csv, glob, json, sys
