@@ -183,7 +183,8 @@ class PerfStruct(C.Structure):
                 ("server_required", C.c_int64), ("server_busy_ms", C.c_double),
                 ("server_payload_bytes", C.c_int64), ("server_chains", C.c_int64),
                 ("server_idle_exits", C.c_int64), ("server_resident_ms", C.c_double),
-                ("intra_sort_launches", C.c_int64), ("intra_sort_ms", C.c_double)]
+                ("intra_sort_launches", C.c_int64), ("intra_sort_ms", C.c_double),
+                ("accept_launches", C.c_int64), ("accept_cells", C.c_int64), ("accept_kernel_ms", C.c_double)]
 
 
 # ----------------------------------------------------------------------------------------------- errors
@@ -214,12 +215,12 @@ class DeviceError(CruiseControlError):
 _STATUS = {1: IllegalArgumentException, 2: DeviceError, 3: OptimizationFailureException, 4: IllegalStateException,
            5: UnsupportedOperationException}
 
-ABI_VERSION = 12  # CCMI_ABI_VERSION of include/ccmi.h
+ABI_VERSION = 13  # CCMI_ABI_VERSION of include/ccmi.h
 EXPORTED_SYMBOLS = (
     "ccmi_last_error", "ccmi_abi_version", "ccmi_device_count", "ccmi_default_constraint", "ccmi_default_random_cluster_props",
     "ccmi_random_cluster", "ccmi_cluster_buffers_desc", "ccmi_cluster_buffers_free", "ccmi_session_create",
     "ccmi_session_destroy", "ccmi_optimizations", "ccmi_goal_optimize", "ccmi_action_acceptance",
-    "ccmi_action_acceptance_by_kind", "ccmi_session_apply", "ccmi_last_failure_provision",
+    "ccmi_action_acceptance_by_kind", "ccmi_actions_acceptance", "ccmi_session_apply", "ccmi_last_failure_provision",
     "ccmi_compute_cluster_stats", "ccmi_action_log_count", "ccmi_action_log_copy", "ccmi_replica_distribution",
     "ccmi_leader_distribution", "ccmi_replica_disks", "ccmi_proposal_count", "ccmi_proposals",
     "ccmi_proposal_disks", "ccmi_perf", "ccmi_perf_reset",
@@ -262,6 +263,11 @@ class Library:
         L.ccmi_action_acceptance.argtypes = [C.c_void_p, C.c_int32, C.POINTER(ActionStruct), C.POINTER(C.c_int32)]
         L.ccmi_action_acceptance_by_kind.argtypes = [C.c_void_p, C.c_int32, C.POINTER(ActionStruct),
                                                      C.POINTER(C.c_int32)]
+        # the batched call runs on the device only: the CPU tests' emulation build reports the same ABI without it
+        self.has_actions_acceptance = hasattr(L, "ccmi_actions_acceptance")
+        if self.has_actions_acceptance:
+            L.ccmi_actions_acceptance.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(ActionStruct),
+                                                  C.c_int64, C.POINTER(C.c_int8), C.POINTER(C.c_int64)]
         L.ccmi_session_apply.argtypes = [C.c_void_p, C.POINTER(ActionStruct), C.c_int64, C.POINTER(C.c_int64)]
         L.ccmi_last_failure_provision.argtypes = [C.c_void_p, C.POINTER(ProvisionRespStruct)]
         L.ccmi_compute_cluster_stats.argtypes = [C.c_void_p, C.POINTER(ConstraintStruct), C.POINTER(OptionsStruct),
@@ -1140,6 +1146,36 @@ class ClusterModel:
         self.lib.check(self.lib.lib.ccmi_action_acceptance_by_kind(self.handle, GOAL_KINDS[goal_name], C.byref(a),
                                                                    C.byref(out)))
         return ACCEPTANCE[out.value]
+
+    def actions_acceptance(self, goal_names, actions):
+        """Goal.actionAcceptance of several optimized goals for a batch of actions in one device call
+        (ccmi_actions_acceptance): a numpy int8 array [n, G] of ACCEPTANCE indices, cell [i, g] what
+        action_acceptance_by_goal(goal_names[g], *actions[i]) returns. Actions are tuples in the action-log layout
+        (type, partition, source, destination, destination partition, source disk, destination disk) or an [n, 7] int32
+        array. An action the single call refuses raises IllegalArgumentException with its index in `first_invalid`."""
+        import numpy as np
+
+        if not self.lib.has_actions_acceptance:
+            raise UnsupportedOperationException(
+                f"{self.lib.path} does not export ccmi_actions_acceptance: the batched call runs on the device only")
+        names = list(goal_names)
+        acts = np.ascontiguousarray(np.asarray(actions if len(actions) else np.zeros((0, 7)), dtype=np.int32))
+        if acts.ndim != 2 or acts.shape[1] != 7:
+            raise IllegalArgumentException("actions must be [n, 7]: the action-log layout")
+        n, G = acts.shape[0], len(names)
+        kinds = (C.c_int32 * max(1, G))(*[GOAL_KINDS[g] for g in names])
+        out = np.zeros((n, G), dtype=np.int8)
+        bad = C.c_int64(-1)
+        # ActionStruct is seven int32: the array rows are the structs
+        status = self.lib.lib.ccmi_actions_acceptance(
+            self.handle, kinds, G, C.cast(acts.ctypes.data, C.POINTER(ActionStruct)), n,
+            out.ctypes.data_as(C.POINTER(C.c_int8)), C.byref(bad))
+        try:
+            self.lib.check(status)
+        except CruiseControlError as e:
+            e.first_invalid = bad.value
+            raise
+        return out
 
     def apply(self, actions) -> int:
         """Apply actions decided elsewhere (tuples in the action-log layout: type, partition, source,

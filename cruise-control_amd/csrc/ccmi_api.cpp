@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "ccmi.h"
+#include "ccmi_session.h"
 #include "engine/buffers.h"
 #include "engine/device.h"
 #include "engine/engine.h"
@@ -22,38 +23,13 @@ namespace ccmi {
 ccmi_cluster_buffers* generateRandomCluster(const ccmi_random_cluster_props& p);
 }
 
-struct ccmi_session;
-struct ccmi_shard_group {
-  ccmi::CombineBlock* blk = nullptr;
-  int32_t count = 0;
-  // attached sessions by rank; a destroyed session clears its slot and a destroyed group its sessions' back pointers,
-  // so neither side is ever read after it is freed
-  std::vector<ccmi_session*> ranks;
-};
 static void groupDetach(ccmi_session* s);
 
-struct ccmi_session {
-  ~ccmi_session() {
-    groupDetach(this);
-    ccmi::rcclDestroy(rccl);
-    ccmi::shmDestroy(shm);
-  }
-  ccmi::Model model;
-  std::unique_ptr<ccmi::Device> device;
-  std::unique_ptr<ccmi::Engine> engine;
-  ccmi::RcclShard* rccl = nullptr;
-  ccmi::ShmShard* shm = nullptr;
-  ccmi_shard_group* group = nullptr;  // the shard group this session is a rank of (ccmi_session_attach_group)
-  int32_t groupRank = -1;
-  int deviceOrdinal = 0;
-  std::vector<int32_t> initDist, initLeaders;  // for ExecutionProposal diffs
-  std::vector<int32_t> initDisks, initLeaderDisks;  // the logdir half of ReplicaPlacementInfo (JBOD)
-  struct Prop {
-    int32_t partition, size, oldLeader;
-    std::vector<int32_t> oldR, newR, oldD, newD;
-  };
-  std::vector<Prop> proposals;
-};
+ccmi_session::~ccmi_session() {
+  groupDetach(this);
+  ccmi::rcclDestroy(rccl);
+  ccmi::shmDestroy(shm);
+}
 
 static void groupDetach(ccmi_session* s) {
   if (!s->group) return;
@@ -78,27 +54,6 @@ void setLastError(const std::string& msg) { g_err = msg; }
 }  // namespace ccmi
 
 namespace {
-
-template <class F>
-ccmi_status guarded(F&& f) {
-  try {
-    return f();
-  } catch (ccmi::OptimizationFailure& e) {
-    return fail(CCMI_E_OPT_FAILURE, e.what());
-  } catch (ccmi::StateError& e) {
-    return fail(CCMI_E_STATE, e.what());
-  } catch (ccmi::Unsupported& e) {
-    return fail(CCMI_E_UNSUPPORTED, e.what());
-  } catch (std::invalid_argument& e) {
-    return fail(CCMI_E_INVALID, e.what());
-  } catch (std::exception& e) {
-    const std::string w = e.what();
-    return fail(w.rfind("HIP", 0) == 0 || w.find("gfx950") != std::string::npos || w.find("device") != std::string::npos
-                    ? CCMI_E_DEVICE
-                    : CCMI_E_INVALID,
-                w);
-  }
-}
 
 void setOptions(ccmi_session* s, const ccmi_balancing_constraint* c, const ccmi_opt_options* o) {
   ccmi::Engine& e = *s->engine;
@@ -853,6 +808,9 @@ ccmi_status ccmi_perf(const ccmi_session* s, ccmi_perf_counters* out) {
     out->server_chains = p.serverChains;
     out->server_idle_exits = p.serverIdleExits;
     out->server_resident_ms = p.serverResidentMs;
+    out->accept_launches = p.acceptLaunches;
+    out->accept_cells = p.acceptCells;
+    out->accept_kernel_ms = p.acceptKernelMs;
     return CCMI_OK;
   });
 }

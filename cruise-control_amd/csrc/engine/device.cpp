@@ -165,6 +165,9 @@ Device::Device(int ordinal, int B, int R, int P, int T, int maxGoalSlots)
   hipCheck(hipEventCreate((hipEvent_t*)&ev2_), "hipEventCreate");
   hipCheck(hipEventCreate((hipEvent_t*)&evS0_), "hipEventCreate");
   hipCheck(hipEventCreate((hipEvent_t*)&evS1_), "hipEventCreate");
+  // acceptBatch (device_accept.cpp): action rows per launch, whole wavefronts
+  if (const char* ac = std::getenv("CCMI_ACCEPT_CHUNK_ROWS"))
+    acceptChunkRows_ = std::max(64, std::min(1 << 24, (int)std::strtol(ac, nullptr, 10))) / 64 * 64;
   {  // scan server: on unless CCMI_SERVER=0; CCMI_SERVER_BLOCKS sets its workgroups (multiple of 8, <= 512)
     const char* e = std::getenv("CCMI_SERVER");
     serverUsable_ = !(e && e[0] == '0');
@@ -299,6 +302,7 @@ Device::~Device() {
   if (segPool_) (void)hipFree(segPool_);
   if (qdir_) (void)hipFree(qdir_);
   if (dServerT0_) (void)hipFree(dServerT0_);
+  if (dAccept_) (void)hipFree(dAccept_);
   if (hStage_) (void)hipHostFree(hStage_);
   if (hResult_) (void)hipHostFree(hResult_);
   if (ev0_) (void)hipEventDestroy(EV0);

@@ -61,6 +61,9 @@ struct DevicePerf {
   int64_t serverChains = 0;    // K7 chains the running server took as commands (no launch, no server restart)
   int64_t serverApplies = 0;   // apply-only server commands (topic-count deltas before a served scan that reads them)
   double serverResidentMs = 0;  // HIP-event time from each server launch to its exit (kernel timing on)
+  int64_t acceptLaunches = 0;   // K9 accept_actions launches (acceptBatch)
+  int64_t acceptCells = 0;      // (action, goal) cells they answered
+  double acceptKernelMs = 0;    // their HIP-event time (kernel timing on)
 };
 
 // K6 (kernels/intra.hip, intra.h): one intra-broker goal over every broker in one launch.
@@ -245,6 +248,14 @@ class Device {
   void flushOnly();
   void flushPending();
 
+  // K9 (kernels/accept.hip, device_accept.cpp): Goal.actionAcceptance of every goal of `prog` (goals[0, nGoals), each
+  // an actionAcceptance column: no slot is an optimizing goal) for nRows resolved actions. rows[0, nMoveRows) are moves
+  // and leadership moves, rows[nMoveRows, nRows) swaps; both counts are whole wavefronts (the caller pads a segment
+  // with copies of one of its rows). out[row * nGoals + g] receives the ccmi_acceptance value. The pending row updates go
+  // to the tables first; one launch and one stream sync per acceptChunkRows() rows. Not in the test emulation.
+  void acceptBatch(const DevProgram& prog, const AcceptRow* rows, int64_t nRows, int64_t nMoveRows, int8_t* out);
+  int acceptChunkRows() const { return acceptChunkRows_; }
+
   // Disks (JBOD): the static disk / replica tables once per session; setDiskUtil whenever the host changed a disk's
   // utilization; intraRun = one intra-broker goal (K6); statsDisks = the disk part of ClusterModelStats.
   void uploadDisks(int D, const int32_t* bDiskOff, const int32_t* bDisks, const double* dCap, const uint8_t* dAlive,
@@ -365,6 +376,9 @@ class Device {
   bool serverChain(const DevProgram& prog, int mode, const int32_t* a0, int n0, const int32_t* a1, int n1,
                    const int32_t* a2, int n2, int n, int m, int maxAccepts);
   void streamWait(const char* what, double seconds);
+  int8_t* dAccept_ = nullptr;  // acceptBatch verdicts of one chunk [rows][nGoals]
+  size_t acceptCap_ = 0;
+  int acceptChunkRows_ = 1 << 17;  // action rows per launch (CCMI_ACCEPT_CHUNK_ROWS, read at session create)
   int32_t* dRackRes_ = nullptr;  // rackRowsGroups results (+ the evaluated-candidate counter after them)
   size_t rackResCap_ = 0;
   int32_t* dChainReq_ = nullptr;  // SOP_CHAIN request copy in HBM (the chain rereads it per decision)

@@ -1,0 +1,80 @@
+// Device::acceptBatch (device.h): the launcher of K9 accept_actions (kernels/accept.hip). A translation unit of its
+// own, linked into libccmi.so only: the test emulation of Device has no acceptance kernel.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <stdexcept>
+#include <string>
+
+#include "device.h"
+#include "prof.h"
+
+namespace ccmi {
+
+hipError_t launchAcceptActions(const DevTables& T, const DevProgram& prog, const AcceptRow* rows, int64_t nRows,
+                               int8_t* out, hipStream_t st);
+
+namespace {
+void hipCheck(hipError_t e, const char* what) {
+  if (e != hipSuccess) throw std::runtime_error(std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
+}
+// the session's device current for the call (HIP's current device is per host thread), the caller's afterwards
+struct CurrentDevice {
+  int prev = -1;
+  explicit CurrentDevice(int ordinal) {
+    hipCheck(hipGetDevice(&prev), "hipGetDevice");
+    if (prev != ordinal) hipCheck(hipSetDevice(ordinal), "hipSetDevice");
+    else prev = -1;
+  }
+  ~CurrentDevice() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+constexpr double kAcceptWaitSeconds = 120.0;
+}  // namespace
+
+void Device::acceptBatch(const DevProgram& prog, const AcceptRow* rows, int64_t nRows, int64_t nMoveRows, int8_t* out) {
+  CurrentDevice cur(ordinal_);
+  PhaseScope ps(PH_DEV_SCAN);
+  stopServer();  // a plain launch on the session stream (no server is resident between API calls anyway)
+  if (nRows % 64 != 0 || nMoveRows % 64 != 0 || nMoveRows < 0 || nMoveRows > nRows)
+    throw std::logic_error("acceptBatch takes whole wavefronts of each row kind");
+  if (prog.nGoals < 1 || prog.nGoals > kMaxGoals) throw std::logic_error("acceptBatch: goal count");
+  if (nRows == 0) {
+    flushPending();
+    return;
+  }
+  const size_t G = (size_t)prog.nGoals;
+  const int64_t chunk = acceptChunkRows_;  // a multiple of 64, so a chunk boundary never splits a wavefront
+  const hipStream_t st = (hipStream_t)st_;
+  for (int64_t r0 = 0; r0 < nRows; r0 += chunk) {
+    const int64_t n = std::min(chunk, nRows - r0);
+    // the chunk's rows go into HBM with the pending row updates (prep; the first chunk carries them all)
+    const size_t req = (size_t)n * sizeof(AcceptRow);
+    const Staged g = packUpdates(req);
+    std::memcpy(hStage_ + g.end, rows + r0, req);
+    launchPrepFor(g, req, false);
+    if ((size_t)n * G > acceptCap_) {
+      if (dAccept_) hipCheck(hipFree(dAccept_), "hipFree");
+      dAccept_ = nullptr;
+      acceptCap_ = 0;
+      hipCheck(hipMalloc((void**)&dAccept_, (size_t)n * G), "hipMalloc acceptance");
+      acceptCap_ = (size_t)n * G;
+    }
+    if (timing) (void)hipEventRecord((hipEvent_t)ev0_, st);
+    hipCheck(launchAcceptActions(tables(), prog, (const AcceptRow*)dReq_, n, dAccept_, st), "accept_actions");
+    if (timing) (void)hipEventRecord((hipEvent_t)ev1_, st);
+    hipCheck(hipMemcpyAsync(out + (size_t)r0 * G, dAccept_, (size_t)n * G, hipMemcpyDeviceToHost, st), "D2H acceptance");
+    streamWait("accept_actions", kAcceptWaitSeconds);
+    perf.syncs++;
+    perf.acceptLaunches++;  // acceptCells is the caller's count: it knows which rows are padding
+    if (timing) {
+      float ms = 0.f;
+      hipCheck(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_), "hipEventElapsedTime");
+      perf.acceptKernelMs += ms;
+    }
+  }
+}
+
+}  // namespace ccmi

@@ -225,6 +225,13 @@ struct alignas(16) RowRef {
 };
 static_assert(sizeof(RowRef) == 16, "RowRef is one 16-byte load");
 
+// One action of an acceptance batch (kernels/accept.hip) as the host resolved it (Model::replicaOn): the source replica,
+// the swapped replica (-1 unless a swap), the destination broker and the DevAction.
+struct alignas(16) AcceptRow {
+  int32_t sr, dr, dst, action;
+};
+static_assert(sizeof(AcceptRow) == 16, "AcceptRow is one 16-byte load");
+
 struct UpdateList {
   const BrokerRow* brows;
   const ReplicaRow* rrows;

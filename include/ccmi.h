@@ -13,6 +13,8 @@
  *                                 analyzer/goals/Goal.java:60-66, AbstractGoal.java:81-135
  *   ccmi_action_acceptance     <- Goal.actionAcceptance(BalancingAction, ClusterModel)
  *                                 analyzer/goals/Goal.java:68-80
+ *   ccmi_actions_acceptance    <- AnalyzerUtils.isProposalAcceptableForOptimizedGoals for a candidate list
+ *                                 analyzer/AnalyzerUtils.java:169-179 (every goal's verdict, one device call)
  *   ccmi_compute_cluster_stats <- ClusterModel.getClusterStats(BalancingConstraint, OptimizationOptions)
  *                                 model/ClusterModel.java:137-139 -> ClusterModelStats.populate :84-102
  *   ccmi_action_log_*          <- the ordered relocateReplica/relocateLeadership calls a goal makes
@@ -37,7 +39,7 @@
 extern "C" {
 #endif
 
-#define CCMI_ABI_VERSION 12
+#define CCMI_ABI_VERSION 13
 
 typedef enum ccmi_status {
   CCMI_OK = 0,
@@ -440,6 +442,18 @@ ccmi_status ccmi_action_acceptance(ccmi_session* s, int32_t optimized_goal_index
  * has not optimized that kind. */
 ccmi_status ccmi_action_acceptance_by_kind(ccmi_session* s, int32_t goal_kind, const ccmi_action* action,
                                            int32_t* acceptance);
+/* ABI v13. Goal.actionAcceptance for a batch: acceptance[i * num_goals + g] is what
+ * ccmi_action_acceptance_by_kind(s, goal_kinds[g], &actions[i], ..) returns on the session's current model
+ * (a ccmi_acceptance value). The session is not changed. The cells run on the device in one launch per chunk of actions
+ * (a JVM goal late in a mixed chain asks every optimized goal about every candidate, AnalyzerUtils.java:169-179); only
+ * the cells of an intra-broker goal are answered on the host. Errors are those of the single call, decided before
+ * anything runs on the device: a kind the session has not optimized is CCMI_E_INVALID, a goal whose actionAcceptance
+ * throws IllegalStateException CCMI_E_STATE, an action the single call refuses CCMI_E_INVALID with *first_invalid (when
+ * given) set to its index (-1 for every other error). On error the output is unspecified. n == 0 is CCMI_OK; duplicate
+ * kinds give duplicate columns. A sharded session answers locally (every shard holds the whole model). */
+ccmi_status ccmi_actions_acceptance(ccmi_session* s, const int32_t* goal_kinds, int32_t num_goals,
+                                    const ccmi_action* actions, int64_t n, int8_t* acceptance,
+                                    int64_t* first_invalid /* optional */);
 /* Session update by deltas: apply actions decided outside this session (a JVM goal earlier in a mixed chain, an
  * executed proposal batch) to the resident model, in order, as ClusterModel.relocateReplica /
  * relocateLeadership / relocateReplica(tp, broker, logdir) do (a swap is its two relocateReplica calls,
@@ -548,6 +562,11 @@ typedef struct ccmi_perf_counters {
    * HIP-event time intra_kernel_ms now holds alone */
   int64_t intra_sort_launches;
   double intra_sort_ms;
+  /* ABI v13: ccmi_actions_acceptance launches, the cells they answered on the device, and their HIP-event time (with
+   * ccmi_set_kernel_timing on) */
+  int64_t accept_launches;
+  int64_t accept_cells;
+  double accept_kernel_ms;
 } ccmi_perf_counters;
 ccmi_status ccmi_perf(const ccmi_session* s, ccmi_perf_counters* out);
 void ccmi_perf_reset(ccmi_session* s);
