@@ -220,7 +220,8 @@ EXPORTED_SYMBOLS = (
     "ccmi_last_error", "ccmi_abi_version", "ccmi_device_count", "ccmi_default_constraint", "ccmi_default_random_cluster_props",
     "ccmi_random_cluster", "ccmi_cluster_buffers_desc", "ccmi_cluster_buffers_free", "ccmi_session_create",
     "ccmi_session_destroy", "ccmi_optimizations", "ccmi_goal_optimize", "ccmi_action_acceptance",
-    "ccmi_action_acceptance_by_kind", "ccmi_actions_acceptance", "ccmi_session_apply", "ccmi_last_failure_provision",
+    "ccmi_action_acceptance_by_kind", "ccmi_actions_acceptance", "ccmi_moves_acceptance_mask", "ccmi_session_apply",
+    "ccmi_last_failure_provision",
     "ccmi_compute_cluster_stats", "ccmi_action_log_count", "ccmi_action_log_copy", "ccmi_replica_distribution",
     "ccmi_leader_distribution", "ccmi_replica_disks", "ccmi_proposal_count", "ccmi_proposals",
     "ccmi_proposal_disks", "ccmi_perf", "ccmi_perf_reset",
@@ -268,6 +269,10 @@ class Library:
         if self.has_actions_acceptance:
             L.ccmi_actions_acceptance.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(ActionStruct),
                                                   C.c_int64, C.POINTER(C.c_int8), C.POINTER(C.c_int64)]
+        self.has_moves_acceptance_mask = hasattr(L, "ccmi_moves_acceptance_mask")
+        if self.has_moves_acceptance_mask:
+            L.ccmi_moves_acceptance_mask.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int64,
+                                                     C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]
         L.ccmi_session_apply.argtypes = [C.c_void_p, C.POINTER(ActionStruct), C.c_int64, C.POINTER(C.c_int64)]
         L.ccmi_last_failure_provision.argtypes = [C.c_void_p, C.POINTER(ProvisionRespStruct)]
         L.ccmi_compute_cluster_stats.argtypes = [C.c_void_p, C.POINTER(ConstraintStruct), C.POINTER(OptionsStruct),
@@ -1176,6 +1181,41 @@ class ClusterModel:
             e.first_invalid = bad.value
             raise
         return out
+
+    def moves_acceptance_mask(self, goal_names, sources, packed=False):
+        """The destination brokers of a batch of move / leadership sources in one device call
+        (ccmi_moves_acceptance_mask): a numpy bool array [n, B], cell [i, b] true iff b is not the source broker, the
+        action (type, partition, source, b) is legit (GoalUtils.legitMove) and every goal of `goal_names` ACCEPTs it; with
+        packed=True the raw uint64 words [n, W], W = (B + 63) // 64, bit b & 63 of word b >> 6. Sources are (type,
+        partition, source broker) tuples or an [n, 3] int32 array. A source the call refuses raises
+        IllegalArgumentException with its index in `first_invalid`."""
+        import numpy as np
+
+        if not self.lib.has_moves_acceptance_mask:
+            raise UnsupportedOperationException(
+                f"{self.lib.path} does not export ccmi_moves_acceptance_mask: the masks are computed on the device only")
+        names = list(goal_names)
+        src = np.asarray(sources if len(sources) else np.zeros((0, 3)), dtype=np.int32)
+        if src.ndim != 2 or src.shape[1] != 3:
+            raise IllegalArgumentException("sources must be [n, 3]: type, partition, source broker")
+        n, G, B = src.shape[0], len(names), self.desc.num_brokers
+        rows = np.zeros((n, 4), dtype=np.int32)  # ccmi_move_source is four int32: the array rows are the structs
+        rows[:, :3] = src
+        kinds = (C.c_int32 * max(1, G))(*[GOAL_KINDS[g] for g in names])
+        W = (B + 63) // 64
+        words = np.zeros((n, W), dtype=np.uint64)
+        bad = C.c_int64(-1)
+        status = self.lib.lib.ccmi_moves_acceptance_mask(self.handle, kinds, G, rows.ctypes.data, n,
+                                                         words.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(bad))
+        try:
+            self.lib.check(status)
+        except CruiseControlError as e:
+            e.first_invalid = bad.value
+            raise
+        if packed:
+            return words
+        bits = np.unpackbits(words.view(np.uint8).reshape(n, W * 8), axis=1, bitorder="little")
+        return bits[:, :B].astype(bool)
 
     def apply(self, actions) -> int:
         """Apply actions decided elsewhere (tuples in the action-log layout: type, partition, source,

@@ -1,6 +1,8 @@
 // ccmi_actions_acceptance (ABI v13): Goal.actionAcceptance of several optimized goals for a batch of actions, answered
-// on the device (Device::acceptBatch, kernels/accept.hip). A translation unit of its own: it is the only caller of
-// Device::acceptBatch, which the test emulation of Device does not have.
+// on the device (Device::acceptBatch, kernels/accept.hip), and ccmi_moves_acceptance_mask: the destination brokers every
+// optimized goal accepts for a batch of move / leadership sources (Device::maskBatch, kernels/accept_mask.hip). A
+// translation unit of its own: it holds the only callers of those two launchers, which the test emulation of Device
+// does not have.
 #include <algorithm>
 #include <cstring>
 #include <stdexcept>
@@ -136,6 +138,77 @@ extern "C" ccmi_status ccmi_actions_acceptance(ccmi_session* s, const int32_t* g
         for (int g = 0; g < G; ++g) acceptance[i * num_goals + devCols[c0 + g]] = cells[(size_t)r * G + g];
       }
     }
+    return CCMI_OK;
+  });
+}
+
+extern "C" ccmi_status ccmi_moves_acceptance_mask(ccmi_session* s, const int32_t* goal_kinds, int32_t num_goals,
+                                                  const ccmi_move_source* sources, int64_t n, uint64_t* mask,
+                                                  int64_t* first_invalid) {
+  if (first_invalid) *first_invalid = -1;
+  return guarded([&] {
+    if (!s) throw std::invalid_argument("null session");
+    if (num_goals < 0 || n < 0) throw std::invalid_argument("negative count");
+    if ((num_goals > 0 && !goal_kinds) || (n > 0 && (!sources || !mask))) throw std::invalid_argument("null argument");
+    ccmi::Engine& e = *s->engine;
+    // each kind is the session's latest optimization of it; a kind named twice is evaluated twice (a conjunction)
+    std::vector<const ccmi::GoalImpl*> goals;
+    const ccmi::GoalImpl* terminal = nullptr;
+    for (int g = 0; g < num_goals; ++g) {
+      if (ccmi::isIntraGoalKind(goal_kinds[g]))
+        throw ccmi::Unsupported("goal kind " + std::to_string(goal_kinds[g]) +
+                                " is an intra-broker goal: it shares no chain with inter-broker goals and has no "
+                                "destination-broker mask; ccmi_actions_acceptance answers its cells on the host");
+      const ccmi::GoalImpl* goal = e.optimizedOfKind(goal_kinds[g]);
+      if (!goal) throw std::invalid_argument("the session has not optimized goal kind " + std::to_string(goal_kinds[g]));
+      if (!terminal && goal->terminal) terminal = goal;
+      goals.push_back(goal);
+    }
+    if (n == 0) return CCMI_OK;
+    if (terminal) throw ccmi::StateError("No goal should be executed after " + terminal->name);
+    // every source against the model before anything runs on the device (the kernel trusts its rows)
+    const ccmi::Model& m = s->model;
+    std::vector<ccmi::MaskRow> rows((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+      const ccmi_move_source& a = sources[i];
+      try {
+        if (a.type != CCMI_INTER_BROKER_REPLICA_MOVEMENT && a.type != CCMI_LEADERSHIP_MOVEMENT)
+          throw std::invalid_argument("a move source is a replica movement or a leadership movement, not action type " +
+                                      std::to_string(a.type));
+        if (a.partition < 0 || a.partition >= m.P) throw std::invalid_argument("partition out of range");
+        if (a.source_broker < 0 || a.source_broker >= m.B) throw std::invalid_argument("broker out of range");
+        const int sr = m.replicaOn(a.partition, a.source_broker);
+        if (sr < 0) throw std::invalid_argument("no replica of the partition on the source broker");
+        rows[(size_t)i] = ccmi::MaskRow{sr, a.partition, a.source_broker,
+                                        a.type == CCMI_LEADERSHIP_MOVEMENT ? ccmi::DA_LEADERSHIP : ccmi::DA_MOVE};
+      } catch (std::invalid_argument&) {
+        if (first_invalid) *first_invalid = i;
+        throw;
+      }
+    }
+    const ccmi::ThreadPin pin(s->deviceOrdinal);  // restored when the call returns
+    s->model.flushToDevice();  // the rows the host changed since the last launch (ccmi_session_apply, a goal's moves)
+    const size_t words = (size_t)n * (size_t)s->device->maskWords();
+    std::vector<uint64_t> part;
+    // one device program per kMaxGoals goals (at least one: without goals, the legit mask); the masks are ANDed
+    for (size_t c0 = 0; c0 == 0 || c0 < goals.size(); c0 += ccmi::kMaxGoals) {
+      const int G = (int)std::min<size_t>(ccmi::kMaxGoals, goals.size() - c0);
+      // every slot is an actionAcceptance column, as in ccmi_actions_acceptance
+      ccmi::DevProgram prog;
+      std::memset(&prog, 0, sizeof(prog));
+      prog.nGoals = G;
+      prog.action = ccmi::DA_MOVE;
+      for (int g = 0; g < G; ++g) prog.goals[g] = goals[c0 + g]->dg;
+      if (c0 == 0) {
+        s->device->maskBatch(prog, rows.data(), n, mask);
+      } else {
+        part.resize(words);
+        s->device->maskBatch(prog, rows.data(), n, part.data());
+        for (size_t w = 0; w < words; ++w) mask[w] &= part[w];
+      }
+    }
+    // the cells the masks stand for, early exits included
+    s->device->perf.acceptCells += n * (int64_t)m.B * num_goals;
     return CCMI_OK;
   });
 }

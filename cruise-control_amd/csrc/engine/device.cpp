@@ -168,6 +168,9 @@ Device::Device(int ordinal, int B, int R, int P, int T, int maxGoalSlots)
   // acceptBatch (device_accept.cpp): action rows per launch, whole wavefronts
   if (const char* ac = std::getenv("CCMI_ACCEPT_CHUNK_ROWS"))
     acceptChunkRows_ = std::max(64, std::min(1 << 24, (int)std::strtol(ac, nullptr, 10))) / 64 * 64;
+  // maskBatch (device_accept.cpp): sources per launch
+  if (const char* mc = std::getenv("CCMI_MASK_CHUNK_SOURCES"))
+    maskChunkSources_ = std::max(1, std::min(1 << 20, (int)std::strtol(mc, nullptr, 10)));
   {  // scan server: on unless CCMI_SERVER=0; CCMI_SERVER_BLOCKS sets its workgroups (multiple of 8, <= 512)
     const char* e = std::getenv("CCMI_SERVER");
     serverUsable_ = !(e && e[0] == '0');

@@ -255,6 +255,13 @@ class Device {
   // to the tables first; one launch and one stream sync per acceptChunkRows() rows. Not in the test emulation.
   void acceptBatch(const DevProgram& prog, const AcceptRow* rows, int64_t nRows, int64_t nMoveRows, int8_t* out);
   int acceptChunkRows() const { return acceptChunkRows_; }
+  // K10 (kernels/accept_mask.hip, device_accept.cpp): for each of nSources resolved move / leadership sources the mask
+  // of destination brokers that are legit and that every goal of `prog` (goals[0, nGoals), nGoals >= 0, each an
+  // actionAcceptance column) ACCEPTs: out[source * W + (b >> 6)] bit (b & 63), W = maskWords(); bits of brokers >= B are
+  // 0. The pending row updates go to the tables first; one launch and one stream sync per CCMI_MASK_CHUNK_SOURCES sources.
+  // Not in the test emulation.
+  void maskBatch(const DevProgram& prog, const MaskRow* rows, int64_t nSources, uint64_t* out);
+  int maskWords() const { return (B_ + 63) / 64; }
 
   // Disks (JBOD): the static disk / replica tables once per session; setDiskUtil whenever the host changed a disk's
   // utilization; intraRun = one intra-broker goal (K6); statsDisks = the disk part of ClusterModelStats.
@@ -376,9 +383,11 @@ class Device {
   bool serverChain(const DevProgram& prog, int mode, const int32_t* a0, int n0, const int32_t* a1, int n1,
                    const int32_t* a2, int n2, int n, int m, int maxAccepts);
   void streamWait(const char* what, double seconds);
-  int8_t* dAccept_ = nullptr;  // acceptBatch verdicts of one chunk [rows][nGoals]
+  int8_t* dAccept_ = nullptr;  // one chunk's acceptBatch verdicts [rows][nGoals] or maskBatch words [sources][W]
   size_t acceptCap_ = 0;
+  void ensureAccept(size_t bytes);
   int acceptChunkRows_ = 1 << 17;  // action rows per launch (CCMI_ACCEPT_CHUNK_ROWS, read at session create)
+  int maskChunkSources_ = 4096;    // sources per launch (CCMI_MASK_CHUNK_SOURCES, read at session create)
   int32_t* dRackRes_ = nullptr;  // rackRowsGroups results (+ the evaluated-candidate counter after them)
   size_t rackResCap_ = 0;
   int32_t* dChainReq_ = nullptr;  // SOP_CHAIN request copy in HBM (the chain rereads it per decision)

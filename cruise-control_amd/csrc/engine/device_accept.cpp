@@ -1,5 +1,6 @@
-// Device::acceptBatch (device.h): the launcher of K9 accept_actions (kernels/accept.hip). A translation unit of its
-// own, linked into libccmi.so only: the test emulation of Device has no acceptance kernel.
+// Device::acceptBatch and Device::maskBatch (device.h): the launchers of K9 accept_actions (kernels/accept.hip) and K10
+// accept_mask (kernels/accept_mask.hip). A translation unit of its own, linked into libccmi.so only: the test emulation
+// of Device has no acceptance kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,6 +15,8 @@ namespace ccmi {
 
 hipError_t launchAcceptActions(const DevTables& T, const DevProgram& prog, const AcceptRow* rows, int64_t nRows,
                                int8_t* out, hipStream_t st);
+hipError_t launchAcceptMask(const DevTables& T, const DevProgram& prog, const MaskRow* rows, int64_t nSources,
+                            unsigned long long* out, hipStream_t st);
 
 namespace {
 void hipCheck(hipError_t e, const char* what) {
@@ -33,6 +36,16 @@ struct CurrentDevice {
 };
 constexpr double kAcceptWaitSeconds = 120.0;
 }  // namespace
+
+// the output buffer of one chunk, grown to the largest chunk so far
+void Device::ensureAccept(size_t bytes) {
+  if (bytes <= acceptCap_) return;
+  if (dAccept_) hipCheck(hipFree(dAccept_), "hipFree");
+  dAccept_ = nullptr;
+  acceptCap_ = 0;
+  hipCheck(hipMalloc((void**)&dAccept_, bytes), "hipMalloc acceptance");
+  acceptCap_ = bytes;
+}
 
 void Device::acceptBatch(const DevProgram& prog, const AcceptRow* rows, int64_t nRows, int64_t nMoveRows, int8_t* out) {
   CurrentDevice cur(ordinal_);
@@ -55,13 +68,7 @@ void Device::acceptBatch(const DevProgram& prog, const AcceptRow* rows, int64_t 
     const Staged g = packUpdates(req);
     std::memcpy(hStage_ + g.end, rows + r0, req);
     launchPrepFor(g, req, false);
-    if ((size_t)n * G > acceptCap_) {
-      if (dAccept_) hipCheck(hipFree(dAccept_), "hipFree");
-      dAccept_ = nullptr;
-      acceptCap_ = 0;
-      hipCheck(hipMalloc((void**)&dAccept_, (size_t)n * G), "hipMalloc acceptance");
-      acceptCap_ = (size_t)n * G;
-    }
+    ensureAccept((size_t)n * G);
     if (timing) (void)hipEventRecord((hipEvent_t)ev0_, st);
     hipCheck(launchAcceptActions(tables(), prog, (const AcceptRow*)dReq_, n, dAccept_, st), "accept_actions");
     if (timing) (void)hipEventRecord((hipEvent_t)ev1_, st);
@@ -69,6 +76,42 @@ void Device::acceptBatch(const DevProgram& prog, const AcceptRow* rows, int64_t 
     streamWait("accept_actions", kAcceptWaitSeconds);
     perf.syncs++;
     perf.acceptLaunches++;  // acceptCells is the caller's count: it knows which rows are padding
+    if (timing) {
+      float ms = 0.f;
+      hipCheck(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_), "hipEventElapsedTime");
+      perf.acceptKernelMs += ms;
+    }
+  }
+}
+
+void Device::maskBatch(const DevProgram& prog, const MaskRow* rows, int64_t nSources, uint64_t* out) {
+  CurrentDevice cur(ordinal_);
+  PhaseScope ps(PH_DEV_SCAN);
+  stopServer();  // a plain launch on the session stream, as acceptBatch
+  if (nSources < 0 || prog.nGoals < 0 || prog.nGoals > kMaxGoals) throw std::logic_error("maskBatch: counts");
+  if (nSources == 0) {
+    flushPending();
+    return;
+  }
+  const size_t W = (size_t)maskWords();
+  const int64_t chunk = maskChunkSources_;
+  const hipStream_t st = (hipStream_t)st_;
+  for (int64_t s0 = 0; s0 < nSources; s0 += chunk) {
+    const int64_t n = std::min(chunk, nSources - s0);
+    // the chunk's sources go into HBM with the pending row updates (prep; the first chunk carries them all)
+    const size_t req = (size_t)n * sizeof(MaskRow);
+    const Staged g = packUpdates(req);
+    std::memcpy(hStage_ + g.end, rows + s0, req);
+    launchPrepFor(g, req, false);
+    const size_t bytes = (size_t)n * W * sizeof(uint64_t);
+    ensureAccept(bytes);
+    if (timing) (void)hipEventRecord((hipEvent_t)ev0_, st);
+    hipCheck(launchAcceptMask(tables(), prog, (const MaskRow*)dReq_, n, (unsigned long long*)dAccept_, st), "accept_mask");
+    if (timing) (void)hipEventRecord((hipEvent_t)ev1_, st);
+    hipCheck(hipMemcpyAsync(out + (size_t)s0 * W, dAccept_, bytes, hipMemcpyDeviceToHost, st), "D2H masks");
+    streamWait("accept_mask", kAcceptWaitSeconds);
+    perf.syncs++;
+    perf.acceptLaunches++;  // acceptCells is the caller's count
     if (timing) {
       float ms = 0.f;
       hipCheck(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_), "hipEventElapsedTime");

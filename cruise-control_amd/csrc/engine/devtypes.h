@@ -232,6 +232,13 @@ struct alignas(16) AcceptRow {
 };
 static_assert(sizeof(AcceptRow) == 16, "AcceptRow is one 16-byte load");
 
+// One source of a destination-mask batch (kernels/accept_mask.hip) as the host resolved it: the replica of partition p
+// on broker src that moves or gives up leadership, and the DevAction (DA_MOVE or DA_LEADERSHIP).
+struct alignas(16) MaskRow {
+  int32_t sr, p, src, action;
+};
+static_assert(sizeof(MaskRow) == 16, "MaskRow is one 16-byte load");
+
 struct UpdateList {
   const BrokerRow* brows;
   const ReplicaRow* rrows;

@@ -15,6 +15,8 @@
  *                                 analyzer/goals/Goal.java:68-80
  *   ccmi_actions_acceptance    <- AnalyzerUtils.isProposalAcceptableForOptimizedGoals for a candidate list
  *                                 analyzer/AnalyzerUtils.java:169-179 (every goal's verdict, one device call)
+ *   ccmi_moves_acceptance_mask <- the candidate loop of AbstractGoal.maybeApplyBalancingAction
+ *                                 analyzer/goals/AbstractGoal.java:243-270 (legit and accepted brokers as bit masks)
  *   ccmi_compute_cluster_stats <- ClusterModel.getClusterStats(BalancingConstraint, OptimizationOptions)
  *                                 model/ClusterModel.java:137-139 -> ClusterModelStats.populate :84-102
  *   ccmi_action_log_*          <- the ordered relocateReplica/relocateLeadership calls a goal makes
@@ -454,6 +456,37 @@ ccmi_status ccmi_action_acceptance_by_kind(ccmi_session* s, int32_t goal_kind, c
 ccmi_status ccmi_actions_acceptance(ccmi_session* s, const int32_t* goal_kinds, int32_t num_goals,
                                     const ccmi_action* actions, int64_t n, int8_t* acceptance,
                                     int64_t* first_invalid /* optional */);
+/* One source of a destination-broker mask: the replica of `partition` on `source_broker` that moves
+ * (CCMI_INTER_BROKER_REPLICA_MOVEMENT) or gives up leadership (CCMI_LEADERSHIP_MOVEMENT). */
+typedef struct ccmi_move_source {
+  int32_t type;           /* CCMI_INTER_BROKER_REPLICA_MOVEMENT or CCMI_LEADERSHIP_MOVEMENT */
+  int32_t partition;      /* partition index (desc order) */
+  int32_t source_broker;  /* the broker whose replica of the partition moves / gives up leadership */
+  int32_t reserved;       /* 0 */
+} ccmi_move_source;
+/* Additive at ABI v13 (the capability flag is the presence of the symbol). The destination brokers of a replica-move or
+ * leadership-move loop (AbstractGoal.maybeApplyBalancingAction, AbstractGoal.java:243-270) for a batch of sources, one
+ * bit per broker: with W = (num_brokers + 63) / 64, bit (b & 63) of mask[i * W + (b >> 6)] is set iff
+ * b != sources[i].source_broker, GoalUtils.legitMove holds for (the source replica, broker b, the type) — a replica move:
+ * b neither hosts the partition nor is one of its ineligible brokers; a leadership move: the source replica is the leader
+ * and b hosts a replica of the partition — and every goal of goal_kinds (each the session's latest optimization of that
+ * kind) returns ACCEPT for that action on the session's current model; either reject code clears the bit. Bits of
+ * positions >= num_brokers are 0. num_goals == 0 gives the pure legit mask; duplicate kinds are harmless; any number of
+ * goals is allowed. The session is not changed. The whole grid runs on the device (one wavefront per output word); the
+ * host does no per-candidate work. The option filters of GoalUtils.eligibleBrokers (excluded brokers, NEW brokers,
+ * requested destinations) stay the caller's: it ANDs the mask with its own candidate set. Swap candidates are replica
+ * pairs and stay with the batched verdict call above.
+ * Errors, all decided before anything runs on the device: CCMI_E_UNSUPPORTED for an intra-broker goal kind (such goals
+ * share no chain with inter-broker goals; their host-answered cells stay with the batched verdict call),
+ * CCMI_E_INVALID for a kind the session has not optimized, CCMI_E_STATE for a goal whose actionAcceptance throws
+ * IllegalStateException, CCMI_E_INVALID with *first_invalid (when given) set to the source's index for a source of
+ * another action type, with a partition or broker out of range, or without a replica of the partition on the source
+ * broker; *first_invalid is -1 for every other error and on success. On error the output is unspecified. n == 0 is
+ * CCMI_OK. A sharded session answers locally. */
+ccmi_status ccmi_moves_acceptance_mask(ccmi_session* s, const int32_t* goal_kinds, int32_t num_goals,
+                                       const ccmi_move_source* sources, int64_t n,
+                                       uint64_t* mask /* [n * W], W = (num_brokers + 63) / 64 */,
+                                       int64_t* first_invalid /* optional */);
 /* Session update by deltas: apply actions decided outside this session (a JVM goal earlier in a mixed chain, an
  * executed proposal batch) to the resident model, in order, as ClusterModel.relocateReplica /
  * relocateLeadership / relocateReplica(tp, broker, logdir) do (a swap is its two relocateReplica calls,
