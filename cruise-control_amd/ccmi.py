@@ -77,6 +77,8 @@ BROKER_SET_POLICIES = {"TopicNameHashBrokerSetMappingPolicy": 0, "ReplicaToOrigi
 ACTION_TYPES = ("INTER_BROKER_REPLICA_MOVEMENT", "LEADERSHIP_MOVEMENT", "INTER_BROKER_REPLICA_SWAP",
                 "INTRA_BROKER_REPLICA_MOVEMENT", "INTRA_BROKER_REPLICA_SWAP")
 ACCEPTANCE = ("ACCEPT", "REPLICA_REJECT", "BROKER_REJECT")
+# ccmi_swap_code: the cells of ClusterModel.swaps_acceptance_grid
+SWAP_CODES = ["ACCEPT", "REPLICA_REJECT", "BROKER_REJECT", "SOURCE_NOT_LEGIT", "CANDIDATE_NOT_LEGIT"]
 
 
 # ----------------------------------------------------------------------------------------------- ctypes layouts
@@ -220,8 +222,8 @@ EXPORTED_SYMBOLS = (
     "ccmi_last_error", "ccmi_abi_version", "ccmi_device_count", "ccmi_default_constraint", "ccmi_default_random_cluster_props",
     "ccmi_random_cluster", "ccmi_cluster_buffers_desc", "ccmi_cluster_buffers_free", "ccmi_session_create",
     "ccmi_session_destroy", "ccmi_optimizations", "ccmi_goal_optimize", "ccmi_action_acceptance",
-    "ccmi_action_acceptance_by_kind", "ccmi_actions_acceptance", "ccmi_moves_acceptance_mask", "ccmi_session_apply",
-    "ccmi_last_failure_provision",
+    "ccmi_action_acceptance_by_kind", "ccmi_actions_acceptance", "ccmi_moves_acceptance_mask", "ccmi_swaps_acceptance_grid",
+    "ccmi_session_apply", "ccmi_last_failure_provision",
     "ccmi_compute_cluster_stats", "ccmi_action_log_count", "ccmi_action_log_copy", "ccmi_replica_distribution",
     "ccmi_leader_distribution", "ccmi_replica_disks", "ccmi_proposal_count", "ccmi_proposals",
     "ccmi_proposal_disks", "ccmi_perf", "ccmi_perf_reset",
@@ -273,6 +275,10 @@ class Library:
         if self.has_moves_acceptance_mask:
             L.ccmi_moves_acceptance_mask.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int64,
                                                      C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]
+        self.has_swaps_acceptance_grid = hasattr(L, "ccmi_swaps_acceptance_grid")
+        if self.has_swaps_acceptance_grid:
+            L.ccmi_swaps_acceptance_grid.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int64,
+                                                     C.c_void_p, C.c_int64, C.POINTER(C.c_int8), C.POINTER(C.c_int64)]
         L.ccmi_session_apply.argtypes = [C.c_void_p, C.POINTER(ActionStruct), C.c_int64, C.POINTER(C.c_int64)]
         L.ccmi_last_failure_provision.argtypes = [C.c_void_p, C.POINTER(ProvisionRespStruct)]
         L.ccmi_compute_cluster_stats.argtypes = [C.c_void_p, C.POINTER(ConstraintStruct), C.POINTER(OptionsStruct),
@@ -1216,6 +1222,40 @@ class ClusterModel:
             return words
         bits = np.unpackbits(words.view(np.uint8).reshape(n, W * 8), axis=1, bitorder="little")
         return bits[:, :B].astype(bool)
+
+    def swaps_acceptance_grid(self, goal_names, sources, candidates):
+        """The swap candidates of a batch of source replicas in one device call (ccmi_swaps_acceptance_grid): a numpy
+        int8 array [n, m], cell [i, j] the SWAP_CODES index of swapping source replica i with candidate replica j —
+        SOURCE_NOT_LEGIT / CANDIDATE_NOT_LEGIT when GoalUtils.legitMove fails for the source to the candidate's broker /
+        for the candidate to the source's broker, else the first verdict of `goal_names`, in that order, that is not
+        ACCEPT, else ACCEPT. Sources and candidates are (partition, broker) tuples or [k, 2] int32 arrays. A replica the
+        call refuses raises IllegalArgumentException with `first_invalid` = i for a source, n + j for a candidate."""
+        import numpy as np
+
+        if not self.lib.has_swaps_acceptance_grid:
+            raise UnsupportedOperationException(
+                f"{self.lib.path} does not export ccmi_swaps_acceptance_grid: the grid is computed on the device only")
+        names = list(goal_names)
+
+        def replicas(what, rows):  # ccmi_swap_replica is two int32: the array rows are the structs
+            a = np.ascontiguousarray(rows if len(rows) else np.zeros((0, 2)), dtype=np.int32)
+            if a.ndim != 2 or a.shape[1] != 2:
+                raise IllegalArgumentException(f"{what} must be [k, 2]: partition, broker")
+            return a
+
+        src, cand = replicas("sources", sources), replicas("candidates", candidates)
+        n, m, G = src.shape[0], cand.shape[0], len(names)
+        kinds = (C.c_int32 * max(1, G))(*[GOAL_KINDS[g] for g in names])
+        codes = np.zeros((n, m), dtype=np.int8)
+        bad = C.c_int64(-1)
+        status = self.lib.lib.ccmi_swaps_acceptance_grid(self.handle, kinds, G, src.ctypes.data, n, cand.ctypes.data, m,
+                                                         codes.ctypes.data_as(C.POINTER(C.c_int8)), C.byref(bad))
+        try:
+            self.lib.check(status)
+        except CruiseControlError as e:
+            e.first_invalid = bad.value
+            raise
+        return codes
 
     def apply(self, actions) -> int:
         """Apply actions decided elsewhere (tuples in the action-log layout: type, partition, source,

@@ -1,8 +1,9 @@
 // ccmi_actions_acceptance (ABI v13): Goal.actionAcceptance of several optimized goals for a batch of actions, answered
 // on the device (Device::acceptBatch, kernels/accept.hip), and ccmi_moves_acceptance_mask: the destination brokers every
-// optimized goal accepts for a batch of move / leadership sources (Device::maskBatch, kernels/accept_mask.hip). A
-// translation unit of its own: it holds the only callers of those two launchers, which the test emulation of Device
-// does not have.
+// optimized goal accepts for a batch of move / leadership sources (Device::maskBatch, kernels/accept_mask.hip), and
+// ccmi_swaps_acceptance_grid: one code per (source replica, candidate replica) pair of a swap loop
+// (Device::swapGridBatch, kernels/accept_swap.hip). A translation unit of its own: it holds the only callers of those
+// three launchers, which the test emulation of Device does not have.
 #include <algorithm>
 #include <cstring>
 #include <stdexcept>
@@ -209,6 +210,82 @@ extern "C" ccmi_status ccmi_moves_acceptance_mask(ccmi_session* s, const int32_t
     }
     // the cells the masks stand for, early exits included
     s->device->perf.acceptCells += n * (int64_t)m.B * num_goals;
+    return CCMI_OK;
+  });
+}
+
+extern "C" ccmi_status ccmi_swaps_acceptance_grid(ccmi_session* s, const int32_t* goal_kinds, int32_t num_goals,
+                                                  const ccmi_swap_replica* sources, int64_t n,
+                                                  const ccmi_swap_replica* candidates, int64_t m, int8_t* codes,
+                                                  int64_t* first_invalid) {
+  if (first_invalid) *first_invalid = -1;
+  return guarded([&] {
+    if (!s) throw std::invalid_argument("null session");
+    if (num_goals < 0 || n < 0 || m < 0) throw std::invalid_argument("negative count");
+    if ((num_goals > 0 && !goal_kinds) || (n > 0 && !sources) || (m > 0 && !candidates) || (n > 0 && m > 0 && !codes))
+      throw std::invalid_argument("null argument");
+    ccmi::Engine& e = *s->engine;
+    // each kind is the session's latest optimization of it, in the caller's order: the code is the first verdict that
+    // is not ACCEPT
+    std::vector<const ccmi::GoalImpl*> goals;
+    const ccmi::GoalImpl* terminal = nullptr;
+    for (int g = 0; g < num_goals; ++g) {
+      if (ccmi::isIntraGoalKind(goal_kinds[g]))
+        throw ccmi::Unsupported("goal kind " + std::to_string(goal_kinds[g]) +
+                                " is an intra-broker goal: it shares no chain with inter-broker goals and has no "
+                                "swap grid; ccmi_actions_acceptance answers its cells on the host");
+      const ccmi::GoalImpl* goal = e.optimizedOfKind(goal_kinds[g]);
+      if (!goal) throw std::invalid_argument("the session has not optimized goal kind " + std::to_string(goal_kinds[g]));
+      if (!terminal && goal->terminal) terminal = goal;
+      goals.push_back(goal);
+    }
+    if (n == 0 || m == 0) return CCMI_OK;
+    if (terminal) throw ccmi::StateError("No goal should be executed after " + terminal->name);
+    // every replica against the model before anything runs on the device (the kernel trusts its rows): n + m
+    // resolutions, sources first
+    const ccmi::Model& md = s->model;
+    auto resolve = [&](const ccmi_swap_replica& a, int64_t index) {
+      try {
+        if (a.partition < 0 || a.partition >= md.P) throw std::invalid_argument("partition out of range");
+        if (a.broker < 0 || a.broker >= md.B) throw std::invalid_argument("broker out of range");
+        const int r = md.replicaOn(a.partition, a.broker);
+        if (r < 0) throw std::invalid_argument("no replica of the partition on the broker");
+        return r;
+      } catch (std::invalid_argument&) {
+        if (first_invalid) *first_invalid = index;
+        throw;
+      }
+    };
+    std::vector<ccmi::SwapRow> rows((size_t)n);
+    for (int64_t i = 0; i < n; ++i)
+      rows[(size_t)i] = ccmi::SwapRow{resolve(sources[i], i), sources[i].partition, sources[i].broker, ccmi::DA_SWAP};
+    std::vector<int32_t> cands((size_t)m);
+    for (int64_t j = 0; j < m; ++j) cands[(size_t)j] = resolve(candidates[j], n + j);
+    const ccmi::ThreadPin pin(s->deviceOrdinal);  // restored when the call returns
+    s->model.flushToDevice();  // the rows the host changed since the last launch (ccmi_session_apply, a goal's moves)
+    const size_t cells = (size_t)n * (size_t)m;
+    std::vector<int8_t> part;
+    // one device program per kMaxGoals goals (at least one: without goals, the legitimacy grid). Codes 3 and 4 are the
+    // same in every program; a cell still at 0 takes the next program's code
+    for (size_t c0 = 0; c0 == 0 || c0 < goals.size(); c0 += ccmi::kMaxGoals) {
+      const int G = (int)std::min<size_t>(ccmi::kMaxGoals, goals.size() - c0);
+      // every slot is an actionAcceptance column, as in ccmi_actions_acceptance
+      ccmi::DevProgram prog;
+      std::memset(&prog, 0, sizeof(prog));
+      prog.nGoals = G;
+      prog.action = ccmi::DA_SWAP;
+      for (int g = 0; g < G; ++g) prog.goals[g] = goals[c0 + g]->dg;
+      if (c0 == 0) {
+        s->device->swapGridBatch(prog, rows.data(), n, cands.data(), m, codes);
+      } else {
+        part.resize(cells);
+        s->device->swapGridBatch(prog, rows.data(), n, cands.data(), m, part.data());
+        for (size_t c = 0; c < cells; ++c)
+          if (codes[c] == 0) codes[c] = part[c];
+      }
+    }
+    // the cells the codes stand for, early exits included
+    s->device->perf.acceptCells += n * m * num_goals;
     return CCMI_OK;
   });
 }

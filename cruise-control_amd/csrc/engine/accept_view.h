@@ -1,5 +1,5 @@
-// The predicates' view (predicates.h) of the acceptance kernels: K9 accept_actions (kernels/accept.hip) and K10
-// accept_mask (kernels/accept_mask.hip). Device code only.
+// The predicates' view (predicates.h) of the acceptance kernels: K9 accept_actions (kernels/accept.hip), K10
+// accept_mask (kernels/accept_mask.hip) and K11 accept_swaps (kernels/accept_swap.hip). Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -51,6 +51,22 @@ struct AcceptView {
     B1 = T.brokers[dst];
     R1 = R0;
     P1 = P0;
+  }
+  // A swap of replica a.sr (of partition a.p, on broker a.src) with replica `cand`, whose broker is the destination. The
+  // first of each record depends on the row alone (in K11 wave-uniform, scalar registers); the second hangs off the
+  // candidate: its ReplicaRec, then that replica's partition and broker.
+  __device__ __forceinline__ void loadSwap(const DevTables& T, const SwapRow& a, int cand) {
+    t = T;
+    r0 = a.sr;
+    r1 = cand;
+    p0 = a.p;
+    b0 = a.src;
+    R0 = T.replicas[a.sr];
+    P0 = T.parts[a.p];
+    B0 = T.brokers[a.src];
+    R1 = T.replicas[cand];
+    P1 = T.parts[R1.part];
+    B1 = T.brokers[R1.broker];
   }
 
   __device__ __forceinline__ double bu(int b, int res) const { return b == b0 ? pick(B0.util, res) : pick(B1.util, res); }

@@ -171,6 +171,9 @@ Device::Device(int ordinal, int B, int R, int P, int T, int maxGoalSlots)
   // maskBatch (device_accept.cpp): sources per launch
   if (const char* mc = std::getenv("CCMI_MASK_CHUNK_SOURCES"))
     maskChunkSources_ = std::max(1, std::min(1 << 20, (int)std::strtol(mc, nullptr, 10)));
+  // swapGridBatch (device_accept.cpp): padded cells (bytes of output) per launch; a launch takes at least one source
+  if (const char* sc = std::getenv("CCMI_SWAP_CHUNK_CELLS"))
+    swapChunkCells_ = std::max(64ll, std::min(1ll << 30, std::strtoll(sc, nullptr, 10)));
   {  // scan server: on unless CCMI_SERVER=0; CCMI_SERVER_BLOCKS sets its workgroups (multiple of 8, <= 512)
     const char* e = std::getenv("CCMI_SERVER");
     serverUsable_ = !(e && e[0] == '0');

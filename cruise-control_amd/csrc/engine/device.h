@@ -262,6 +262,14 @@ class Device {
   // Not in the test emulation.
   void maskBatch(const DevProgram& prog, const MaskRow* rows, int64_t nSources, uint64_t* out);
   int maskWords() const { return (B_ + 63) / 64; }
+  // K11 (kernels/accept_swap.hip, device_accept.cpp): the swap code of every (source, candidate replica) pair of
+  // nSources resolved sources and m candidate replica ids (1 <= m <= kMaxSwapCandidates) under `prog` (goals[0, nGoals),
+  // nGoals >= 0, each an actionAcceptance column): out[source * m + candidate] = 3 / 4 when the first / second
+  // legitMove fails, else the first non-ACCEPT verdict in goal order, else 0. The pending row updates go to the tables
+  // first; one launch and one stream sync per max(1, min(65535, CCMI_SWAP_CHUNK_CELLS / pitch)) sources, pitch = m
+  // rounded up to 64. Not in the test emulation.
+  void swapGridBatch(const DevProgram& prog, const SwapRow* rows, int64_t nSources, const int32_t* cands, int64_t m,
+                     int8_t* out);
 
   // Disks (JBOD): the static disk / replica tables once per session; setDiskUtil whenever the host changed a disk's
   // utilization; intraRun = one intra-broker goal (K6); statsDisks = the disk part of ClusterModelStats.
@@ -383,11 +391,14 @@ class Device {
   bool serverChain(const DevProgram& prog, int mode, const int32_t* a0, int n0, const int32_t* a1, int n1,
                    const int32_t* a2, int n2, int n, int m, int maxAccepts);
   void streamWait(const char* what, double seconds);
-  int8_t* dAccept_ = nullptr;  // one chunk's acceptBatch verdicts [rows][nGoals] or maskBatch words [sources][W]
+  // one chunk's acceptBatch verdicts [rows][nGoals], maskBatch words [sources][W] or swapGridBatch codes [sources][pitch]
+  int8_t* dAccept_ = nullptr;
   size_t acceptCap_ = 0;
   void ensureAccept(size_t bytes);
   int acceptChunkRows_ = 1 << 17;  // action rows per launch (CCMI_ACCEPT_CHUNK_ROWS, read at session create)
   int maskChunkSources_ = 4096;    // sources per launch (CCMI_MASK_CHUNK_SOURCES, read at session create)
+  std::vector<int8_t> swapHost_;      // one chunk's pitched codes on the host, before the pitch is removed
+  int64_t swapChunkCells_ = 1 << 24;  // padded swap cells per launch (CCMI_SWAP_CHUNK_CELLS, read at session create)
   int32_t* dRackRes_ = nullptr;  // rackRowsGroups results (+ the evaluated-candidate counter after them)
   size_t rackResCap_ = 0;
   int32_t* dChainReq_ = nullptr;  // SOP_CHAIN request copy in HBM (the chain rereads it per decision)

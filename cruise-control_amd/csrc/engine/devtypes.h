@@ -239,6 +239,14 @@ struct alignas(16) MaskRow {
 };
 static_assert(sizeof(MaskRow) == 16, "MaskRow is one 16-byte load");
 
+// One source of a swap grid (kernels/accept_swap.hip) as the host resolved it: the replica of partition p on broker src;
+// action is DA_SWAP. The candidates of the grid are plain replica ids.
+struct alignas(16) SwapRow {
+  int32_t sr, p, src, action;
+};
+static_assert(sizeof(SwapRow) == 16, "SwapRow is one 16-byte load");
+constexpr int64_t kMaxSwapCandidates = INT32_MAX - 63;  // candidates of one grid: the padded row still indexes as int32
+
 struct UpdateList {
   const BrokerRow* brows;
   const ReplicaRow* rrows;

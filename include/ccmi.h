@@ -17,6 +17,8 @@
  *                                 analyzer/AnalyzerUtils.java:169-179 (every goal's verdict, one device call)
  *   ccmi_moves_acceptance_mask <- the candidate loop of AbstractGoal.maybeApplyBalancingAction
  *                                 analyzer/goals/AbstractGoal.java:243-270 (legit and accepted brokers as bit masks)
+ *   ccmi_swaps_acceptance_grid <- the candidate loop of AbstractGoal.maybeApplySwapAction
+ *                                 analyzer/goals/AbstractGoal.java:287-338 (one code per replica pair)
  *   ccmi_compute_cluster_stats <- ClusterModel.getClusterStats(BalancingConstraint, OptimizationOptions)
  *                                 model/ClusterModel.java:137-139 -> ClusterModelStats.populate :84-102
  *   ccmi_action_log_*          <- the ordered relocateReplica/relocateLeadership calls a goal makes
@@ -475,7 +477,7 @@ typedef struct ccmi_move_source {
  * goals is allowed. The session is not changed. The whole grid runs on the device (one wavefront per output word); the
  * host does no per-candidate work. The option filters of GoalUtils.eligibleBrokers (excluded brokers, NEW brokers,
  * requested destinations) stay the caller's: it ANDs the mask with its own candidate set. Swap candidates are replica
- * pairs and stay with the batched verdict call above.
+ * pairs, not brokers: ccmi_swaps_acceptance_grid below answers them.
  * Errors, all decided before anything runs on the device: CCMI_E_UNSUPPORTED for an intra-broker goal kind (such goals
  * share no chain with inter-broker goals; their host-answered cells stay with the batched verdict call),
  * CCMI_E_INVALID for a kind the session has not optimized, CCMI_E_STATE for a goal whose actionAcceptance throws
@@ -486,6 +488,46 @@ typedef struct ccmi_move_source {
 ccmi_status ccmi_moves_acceptance_mask(ccmi_session* s, const int32_t* goal_kinds, int32_t num_goals,
                                        const ccmi_move_source* sources, int64_t n,
                                        uint64_t* mask /* [n * W], W = (num_brokers + 63) / 64 */,
+                                       int64_t* first_invalid /* optional */);
+/* One replica of a swap grid: the replica of `partition` on `broker`. */
+typedef struct ccmi_swap_replica {
+  int32_t partition; /* partition index (desc order) */
+  int32_t broker;    /* broker index */
+} ccmi_swap_replica;
+/* The code of one (source replica, candidate replica) pair of a swap grid, in the order the loop body of
+ * AbstractGoal.maybeApplySwapAction decides it. */
+typedef enum ccmi_swap_code {
+  CCMI_SWAP_ACCEPT = 0,              /* legit both ways and every goal ACCEPTs */
+  CCMI_SWAP_REPLICA_REJECT = 1,      /* first non-ACCEPT verdict in goal_kinds order */
+  CCMI_SWAP_BROKER_REJECT = 2,       /* first non-ACCEPT verdict in goal_kinds order */
+  CCMI_SWAP_SOURCE_NOT_LEGIT = 3,    /* legitMove(source, candidate's broker) fails: AbstractGoal.java:308, return null */
+  CCMI_SWAP_CANDIDATE_NOT_LEGIT = 4  /* legitMove(candidate, source's broker) fails: AbstractGoal.java:313, continue */
+} ccmi_swap_code;
+/* Additive at ABI v13 (the capability flag is the presence of the symbol). The candidate loop of a swap
+ * (AbstractGoal.maybeApplySwapAction, AbstractGoal.java:287-338) for n source replicas against m candidate replicas:
+ * codes[i * m + j] is the ccmi_swap_code of swapping sources[i] with candidates[j], the destination broker being the
+ * candidate's current broker. The checks run in the reference's order. First GoalUtils.legitMove(source, candidate's
+ * broker, INTER_BROKER_REPLICA_MOVEMENT) — the broker neither hosts the source's partition nor is one of its ineligible
+ * brokers — else 3 (also when both checks fail); then legitMove(candidate, source's broker), else 4; then the goals of
+ * goal_kinds in that order (each the session's latest optimization of that kind) on the session's current model: the
+ * code is the first verdict that is not ACCEPT (AnalyzerUtils.isProposalAcceptableForOptimizedGoals,
+ * AnalyzerUtils.java:169-179), or 0 when there is none. The order of goal_kinds matters; a kind named twice is
+ * harmless. num_goals == 0 gives the pure legitimacy grid (codes 0, 3, 4); any number of goals is allowed. A candidate
+ * on the source's own broker, of the source's partition, or equal to the source fails the first check and is 3: no
+ * special cases. Candidates may sit on any mix of brokers (several candidate brokers' replicas in one call) and may
+ * repeat. m is at most 2^31 - 64. The session is not changed. The whole grid runs on the device (one wavefront per 64
+ * candidates of a source); the host resolves n + m replicas and does no per-pair work. The goal's own selfSatisfied and
+ * GoalUtils.eligibleReplicasForSwap (excluded topics and brokers, NEW-broker rules) stay the caller's.
+ * Errors, all decided before anything runs on the device: CCMI_E_UNSUPPORTED for an intra-broker goal kind,
+ * CCMI_E_INVALID for a kind the session has not optimized, CCMI_E_STATE for a goal whose actionAcceptance throws
+ * IllegalStateException, CCMI_E_INVALID with *first_invalid (when given) set to i for sources[i] or n + j for
+ * candidates[j] (sources are checked first) with a partition or broker out of range or without a replica of the
+ * partition on the broker; *first_invalid is -1 for every other error and on success. On error the output is
+ * unspecified. n == 0 or m == 0 is CCMI_OK once the kinds are checked. A sharded session answers locally. */
+ccmi_status ccmi_swaps_acceptance_grid(ccmi_session* s, const int32_t* goal_kinds, int32_t num_goals,
+                                       const ccmi_swap_replica* sources, int64_t n,
+                                       const ccmi_swap_replica* candidates, int64_t m,
+                                       int8_t* codes /* [n * m], codes[i * m + j] */,
                                        int64_t* first_invalid /* optional */);
 /* Session update by deltas: apply actions decided outside this session (a JVM goal earlier in a mixed chain, an
  * executed proposal batch) to the resident model, in order, as ClusterModel.relocateReplica /
