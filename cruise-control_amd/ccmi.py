@@ -189,6 +189,21 @@ class PerfStruct(C.Structure):
                 ("accept_launches", C.c_int64), ("accept_cells", C.c_int64), ("accept_kernel_ms", C.c_double)]
 
 
+class BasicStatsStruct(C.Structure):  # ccmi_basic_stats: one broker's or one host's BasicStats, 128 bytes
+    _fields_ = [("disk_mb", C.c_double), ("disk_pct", C.c_double), ("cpu_pct", C.c_double),
+                ("leader_nw_in_rate", C.c_double), ("follower_nw_in_rate", C.c_double), ("nw_out_rate", C.c_double),
+                ("pnw_out_rate", C.c_double), ("disk_capacity_mb", C.c_double), ("network_in_capacity", C.c_double),
+                ("network_out_capacity", C.c_double), ("num_core", C.c_double),
+                ("replicas", C.c_int32), ("leaders", C.c_int32), ("broker", C.c_int32), ("state", C.c_int32),
+                ("host", C.c_int32), ("rack", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class DiskStatsStruct(C.Structure):  # ccmi_disk_stats: one disk's DiskStats, 40 bytes
+    _fields_ = [("disk_mb", C.c_double), ("disk_pct", C.c_double), ("capacity", C.c_double),
+                ("num_replicas", C.c_int32), ("num_leader_replicas", C.c_int32), ("disk", C.c_int32),
+                ("broker", C.c_int32)]
+
+
 # ----------------------------------------------------------------------------------------------- errors
 class CruiseControlError(RuntimeError):
     pass
@@ -224,7 +239,7 @@ EXPORTED_SYMBOLS = (
     "ccmi_session_destroy", "ccmi_optimizations", "ccmi_goal_optimize", "ccmi_action_acceptance",
     "ccmi_action_acceptance_by_kind", "ccmi_actions_acceptance", "ccmi_moves_acceptance_mask", "ccmi_swaps_acceptance_grid",
     "ccmi_session_apply", "ccmi_last_failure_provision",
-    "ccmi_compute_cluster_stats", "ccmi_action_log_count", "ccmi_action_log_copy", "ccmi_replica_distribution",
+    "ccmi_compute_cluster_stats", "ccmi_broker_stats", "ccmi_action_log_count", "ccmi_action_log_copy", "ccmi_replica_distribution",
     "ccmi_leader_distribution", "ccmi_replica_disks", "ccmi_proposal_count", "ccmi_proposals",
     "ccmi_proposal_disks", "ccmi_perf", "ccmi_perf_reset",
     "ccmi_set_kernel_timing", "ccmi_session_set_shard", "ccmi_rccl_unique_id", "ccmi_session_attach_rccl",
@@ -279,6 +294,9 @@ class Library:
         if self.has_swaps_acceptance_grid:
             L.ccmi_swaps_acceptance_grid.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int64,
                                                      C.c_void_p, C.c_int64, C.POINTER(C.c_int8), C.POINTER(C.c_int64)]
+        self.has_broker_stats = hasattr(L, "ccmi_broker_stats")
+        if self.has_broker_stats:
+            L.ccmi_broker_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
         L.ccmi_session_apply.argtypes = [C.c_void_p, C.POINTER(ActionStruct), C.c_int64, C.POINTER(C.c_int64)]
         L.ccmi_last_failure_provision.argtypes = [C.c_void_p, C.POINTER(ProvisionRespStruct)]
         L.ccmi_compute_cluster_stats.argtypes = [C.c_void_p, C.POINTER(ConstraintStruct), C.POINTER(OptionsStruct),
@@ -647,10 +665,81 @@ class GoalResult:
     provision: Optional[ProvisionResponse] = None  # Goal.provisionResponse after the goal
 
 
+BROKER_STATE_NAMES = ("ALIVE", "DEAD", "NEW", "DEMOTED", "BAD_DISKS")  # ccmi_broker_state order
+
+
+class BrokerStats:
+    """servlet/response/stats/BrokerStats.java as ClusterModel.brokerStats fills it (ClusterModel.java:1303-1309), read
+    from the device tables by ccmi_broker_stats. `brokers`, `hosts` and `disks` are numpy structured arrays with the
+    fields of BasicStatsStruct / DiskStatsStruct: one row per broker in index order, one per distinct host in ascending
+    host index, one per disk in desc order (empty without disks). The isEstimated flag is not carried (the desc holds
+    no capacity-estimation information) and the plain-text table is left to the servlet."""
+
+    BASIC_KEYS = (("DiskMB", "disk_mb"), ("DiskPct", "disk_pct"), ("CpuPct", "cpu_pct"),
+                  ("LeaderNwInRate", "leader_nw_in_rate"), ("FollowerNwInRate", "follower_nw_in_rate"),
+                  ("NwOutRate", "nw_out_rate"), ("PnwOutRate", "pnw_out_rate"), ("Replicas", "replicas"),
+                  ("Leaders", "leaders"), ("DiskCapacityMB", "disk_capacity_mb"),
+                  ("NetworkInCapacity", "network_in_capacity"), ("NetworkOutCapacity", "network_out_capacity"),
+                  ("NumCore", "num_core"))
+
+    def __init__(self, brokers, hosts, disks, broker_ids: Sequence[int], rack_names: Dict[int, str],
+                 host_names: Dict[int, str], logdirs: Sequence[str]):
+        self.brokers, self.hosts, self.disks = brokers, hosts, disks
+        self.broker_ids = list(broker_ids)
+        self.rack_names, self.host_names = dict(rack_names), dict(host_names)
+        self.logdirs = list(logdirs)
+
+    def rack_name(self, rack: int) -> str:
+        return self.rack_names.get(int(rack), str(int(rack)))
+
+    def host_name(self, host: int) -> str:
+        return self.host_names.get(int(host), str(int(host)))
+
+    def _basic(self, row) -> Dict[str, object]:
+        return {key: (int(row[f]) if f in ("replicas", "leaders") else float(row[f])) for key, f in self.BASIC_KEYS}
+
+    def get_json_structure(self) -> Dict[str, object]:
+        """BrokerStats.getJsonStructure (BrokerStats.java:92-112): the hosts ordered by host name (the reference's
+        ConcurrentSkipListMap), the brokers in id order; a broker with disks carries DiskState by logdir, a dead disk
+        "DEAD" for DiskMB and DiskPct (DiskStats.java:62-65)."""
+        hosts = []
+        for row in self.hosts:
+            e = self._basic(row)
+            e["Host"], e["Rack"] = self.host_name(row["host"]), self.rack_name(row["rack"])
+            hosts.append(e)
+        # hosts are distinct by index (a host is keyed by name within its rack, Rack._hosts): rows that share a name in
+        # different racks stay separate entries, next to each other in host index order (the sort is stable)
+        hosts.sort(key=lambda e: e["Host"])
+        disks_of: Dict[int, Dict[str, object]] = {}
+        for d in self.disks:
+            dead = not d["capacity"] > 0
+            disks_of.setdefault(int(d["broker"]), {})[self.logdirs[int(d["disk"])]] = {
+                "DiskMB": "DEAD" if dead else float(d["disk_mb"]), "DiskPct": "DEAD" if dead else float(d["disk_pct"]),
+                "NumLeaderReplicas": int(d["num_leader_replicas"]), "NumReplicas": int(d["num_replicas"])}
+        brokers = []
+        for row in self.brokers:
+            e = self._basic(row)
+            b = int(row["broker"])
+            e["Host"], e["Broker"] = self.host_name(row["host"]), self.broker_ids[b]
+            e["BrokerState"] = BROKER_STATE_NAMES[int(row["state"])]
+            if b in disks_of:
+                e["DiskState"] = dict(sorted(disks_of[b].items()))  # Broker._diskByLogdir is a TreeMap
+            e["Rack"] = self.rack_name(row["rack"])
+            brokers.append(e)
+        return {"hosts": hosts, "brokers": brokers}
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, BrokerStats) and self.brokers.tobytes() == other.brokers.tobytes()
+                and self.hosts.tobytes() == other.hosts.tobytes() and self.disks.tobytes() == other.disks.tobytes())
+
+    __hash__ = None
+
+
 class OptimizerResult:
     """analyzer/OptimizerResult.java: per-goal results, the ExecutionProposals and the ordered action log. The
-    proposals and the action log are read from the session on first access (the session keeps them until its next
-    optimization), so a caller that only needs the statistics does not pay for converting them."""
+    proposals, the action log and the broker stats after the optimization are read from the session on first access
+    (the session keeps them until its next optimization), so a caller that only needs the statistics does not pay for
+    them."""
 
     def __init__(self, goal_results: List[GoalResult], cluster: "ClusterModel", seconds: float,
                  violated_goals_after: List[str]):
@@ -661,6 +750,27 @@ class OptimizerResult:
         self._num_actions = cluster.lib.lib.ccmi_action_log_count(cluster.handle)
         self._proposals: Optional[List[ExecutionProposal]] = None
         self._actions: Optional[List[tuple]] = None
+        # ClusterModel.brokerStats before the first goal (GoalOptimizer.java:442): taken only when optimizations() was
+        # asked for it
+        self.broker_stats_before_optimization: Optional[BrokerStats] = None
+        self._stats_after: Optional[BrokerStats] = None
+
+    @property
+    def broker_stats_after_optimization(self) -> BrokerStats:
+        """OptimizerResult._brokerStatsAfterOptimization (OptimizerResult.java:111), read from the session on first
+        access, under the same rule as `proposals`."""
+        if self._stats_after is None:
+            self._stats_after = self._cluster.broker_stats()
+        return self._stats_after
+
+    def load_json(self, verbose: bool = False) -> Dict[str, object]:
+        """The load blocks of a rebalance response (OptimizerResult.getJsonStructure): loadAfterOptimization, and in
+        verbose mode loadBeforeOptimization when optimizations() took it."""
+        out: Dict[str, object] = {}
+        if verbose and self.broker_stats_before_optimization is not None:
+            out["loadBeforeOptimization"] = self.broker_stats_before_optimization.get_json_structure()
+        out["loadAfterOptimization"] = self.broker_stats_after_optimization.get_json_structure()
+        return out
 
     @property
     def proposals(self) -> List[ExecutionProposal]:
@@ -984,6 +1094,13 @@ class FlatCluster:
         self.desc = d
         self.topics = list(bld.topics)
         self.partitions = {p: key for key, p in bld.parts.items()}
+        self._rack_names = {i: name for name, i in bld.rack_index.items()}
+        self._host_names = ({self.keep["broker_host"][b]: bld.host[b] for b in range(B) if b in bld.host}
+                            if bld.host else {})
+
+    def stats_names(self):
+        """Rack ids by rack index and host names by host index (a broker created without a host has none)."""
+        return dict(self._rack_names), dict(self._host_names)
 
 
 class LoadMonitorModel:
@@ -1009,6 +1126,19 @@ class LoadMonitorModel:
         self.lib.check(self.lib.lib.ccmi_builder_create(num_windows, C.byref(h)))
         self.handle = h
         self._desc = None
+        self._names: Dict[int, tuple] = {}  # broker id -> (rack, host) as createBroker received them
+
+    def stats_names(self):
+        """Rack ids by rack index and host names by host index, for the brokers create_broker named (a broker only
+        partitions name has neither)."""
+        d = self.desc()
+        racks: Dict[int, str] = {}
+        hosts: Dict[int, str] = {}
+        for b, bid in enumerate(self.broker_ids()):
+            if bid in self._names:
+                racks[d.broker_rack[b]] = self._names[bid][0]
+                hosts[d.broker_host[b] if d.broker_host else b] = self._names[bid][1]
+        return racks, hosts
 
     def __del__(self):
         try:
@@ -1021,6 +1151,7 @@ class LoadMonitorModel:
         cap = (C.c_double * 4)(*[float(capacity[r]) for r in RESOURCES])
         self.lib.check(self.lib.lib.ccmi_builder_create_broker(self.handle, rack.encode(), host.encode(), broker_id,
                                                                cap, 1 if alive else 0))
+        self._names[broker_id] = (rack, host)
         for logdir, c in (disk_capacity_by_logdir or {}).items():
             self.lib.check(self.lib.lib.ccmi_builder_add_disk(self.handle, broker_id, logdir.encode(), float(c)))
 
@@ -1257,6 +1388,33 @@ class ClusterModel:
             raise
         return codes
 
+    def stats_names(self):
+        """(rack names by rack index, host names by host index) from the builder the model was ingested through
+        (FlatCluster / LoadMonitorModel.stats_names); an index without a name is written in decimal."""
+        if hasattr(self._keep, "stats_names"):
+            return self._keep.stats_names()
+        return {}, {}
+
+    def broker_stats(self) -> "BrokerStats":
+        """ClusterModel.brokerStats (ClusterModel.java:1303-1309) of the session's current model in one device call
+        (ccmi_broker_stats): on a fresh session the stats before optimization, after optimizations() or apply() the
+        current ones. The session is not changed."""
+        import numpy as np
+
+        if not self.lib.has_broker_stats:
+            raise UnsupportedOperationException(
+                f"{self.lib.path} does not export ccmi_broker_stats: the stats are computed on the device only")
+        B, D = self.desc.num_brokers, self.desc.num_disks
+        brokers = np.zeros(B, dtype=np.dtype(BasicStatsStruct))
+        hosts = np.zeros(B, dtype=np.dtype(BasicStatsStruct))
+        disks = np.zeros(D, dtype=np.dtype(DiskStatsStruct))
+        nh = C.c_int32(0)
+        self._checked(self.lib.lib.ccmi_broker_stats(self.handle, brokers.ctypes.data, hosts.ctypes.data, C.byref(nh),
+                                                     disks.ctypes.data if D else None))
+        racks, host_names = self.stats_names()
+        logdirs = [self.desc.disk_logdir[d].decode() for d in range(D)]
+        return BrokerStats(brokers, hosts[:nh.value].copy(), disks, self.broker_ids(), racks, host_names, logdirs)
+
     def apply(self, actions) -> int:
         """Apply actions decided elsewhere (tuples in the action-log layout: type, partition, source,
         destination, destination partition, source disk, destination disk) to the resident model
@@ -1409,9 +1567,12 @@ class GoalOptimizer:
         self.strictness_weight = strictness_weight
 
     def optimizations(self, cluster: ClusterModel, goals_by_priority: Sequence[Goal],
-                      options: Optional[OptimizationOptions] = None) -> OptimizerResult:
+                      options: Optional[OptimizationOptions] = None, broker_stats: bool = False) -> OptimizerResult:
+        """broker_stats=True also takes ClusterModel.brokerStats before the first goal (GoalOptimizer.java:442) into
+        OptimizerResult.broker_stats_before_optimization: one more device call. The default issues none."""
         if not goals_by_priority:
             raise IllegalArgumentException("At least one goal must be provided to get an optimization result.")
+        stats_before = cluster.broker_stats() if broker_stats else None
         kinds = (C.c_int32 * len(goals_by_priority))(*[g.kind for g in goals_by_priority])
         results = (GoalResultStruct * len(goals_by_priority))()
         o, keep = (options or OptimizationOptions()).to_struct()
@@ -1425,6 +1586,7 @@ class GoalOptimizer:
                           r.device_candidates, r.device_launches, r.actions, stats_to_dict(r.stats),
                           ProvisionResponse.from_struct(r.provision, GOAL_NAMES[r.goal_kind])) for r in results]
         res = OptimizerResult(grs, cluster, dt, [g.name for g in grs if not g.succeeded])
+        res.broker_stats_before_optimization = stats_before
         res.options = options or OptimizationOptions()
         res.balancedness_cost_by_goal = balancedness_cost_by_goal(goals_by_priority, self.priority_weight,
                                                                   self.strictness_weight)

@@ -309,6 +309,9 @@ Device::~Device() {
   if (qdir_) (void)hipFree(qdir_);
   if (dServerT0_) (void)hipFree(dServerT0_);
   if (dAccept_) (void)hipFree(dAccept_);
+  for (void* p : statsRowAllocs_)  // brokerStats (device_accept.cpp)
+    if (p) (void)hipFree(p);
+  if (dStatMembers_) (void)hipFree(dStatMembers_);
   if (hStage_) (void)hipHostFree(hStage_);
   if (hResult_) (void)hipHostFree(hResult_);
   if (ev0_) (void)hipEventDestroy(EV0);

@@ -20,6 +20,9 @@
 #include "shard_group.h"
 #include "snapseg.h"
 
+struct ccmi_basic_stats;  // include/ccmi.h
+struct ccmi_disk_stats;
+
 namespace ccmi {
 
 
@@ -270,6 +273,20 @@ class Device {
   // rounded up to 64. Not in the test emulation.
   void swapGridBatch(const DevProgram& prog, const SwapRow* rows, int64_t nSources, const int32_t* cands, int64_t m,
                      int8_t* out);
+  // K12 (kernels/broker_stats.hip, device_accept.cpp): ClusterModel.brokerStats from the resident tables.
+  // uploadStatsStatic once per session: every broker's {desc host index, state}, the hosts' brokers as CSR (H hosts in
+  // ascending host index hIdx, a host's brokers ascending) and every disk's broker. brokerStats: the pending row
+  // updates go to the tables first; brokers[B]; hosts[H] unless null; disks[D] unless null or D == 0, its member counts
+  // from members[0, nMembers) ({replica, disk} of every Disk._replicas entry), uploaded only when memberVer differs from
+  // the last call's (setDiskUtil brings the disks' utilization current beforehand). One stream sync, one D2H copy per
+  // output array. Counts into perf.statsLaunches / statsKernelMs / statsBytes. Not in the test emulation.
+  bool statsStaticUploaded() const { return dStatMeta_ != nullptr; }
+  void uploadStatsStatic(const BrokerStatic* meta, int H, const int32_t* hOff, const int32_t* hBrk, const int32_t* hIdx,
+                         const int32_t* dBroker);
+  int statsHosts() const { return statH_; }
+  uint64_t statsMemberVer() const { return statMemberVer_; }
+  void brokerStats(ccmi_basic_stats* brokers, ccmi_basic_stats* hosts, ccmi_disk_stats* disks, const DiskMember* members,
+                   int64_t nMembers, uint64_t memberVer);
 
   // Disks (JBOD): the static disk / replica tables once per session; setDiskUtil whenever the host changed a disk's
   // utilization; intraRun = one intra-broker goal (K6); statsDisks = the disk part of ClusterModelStats.
@@ -399,6 +416,18 @@ class Device {
   int maskChunkSources_ = 4096;    // sources per launch (CCMI_MASK_CHUNK_SOURCES, read at session create)
   std::vector<int8_t> swapHost_;      // one chunk's pitched codes on the host, before the pitch is removed
   int64_t swapChunkCells_ = 1 << 24;  // padded swap cells per launch (CCMI_SWAP_CHUNK_CELLS, read at session create)
+  // brokerStats: static tables, the output rows in HBM ([B] broker rows | [H] host rows, [D] disk rows) and the member
+  // list of the disks with the Model::diskMemberVer it was built at (0 = none)
+  BrokerStatic* dStatMeta_ = nullptr;
+  int32_t *dStatHOff_ = nullptr, *dStatHBrk_ = nullptr, *dStatHIdx_ = nullptr, *dStatDBroker_ = nullptr;
+  ccmi_basic_stats* dStatRows_ = nullptr;
+  ccmi_disk_stats* dStatDisks_ = nullptr;
+  DiskMember* dStatMembers_ = nullptr;
+  size_t statMembersCap_ = 0;
+  int64_t statMembers_ = 0;
+  uint64_t statMemberVer_ = 0;
+  int statH_ = 0;
+  std::vector<void*> statsRowAllocs_;
   int32_t* dRackRes_ = nullptr;  // rackRowsGroups results (+ the evaluated-candidate counter after them)
   size_t rackResCap_ = 0;
   int32_t* dChainReq_ = nullptr;  // SOP_CHAIN request copy in HBM (the chain rereads it per decision)

@@ -1,6 +1,7 @@
 // Device::acceptBatch, Device::maskBatch and Device::swapGridBatch (device.h): the launchers of K9 accept_actions
-// (kernels/accept.hip), K10 accept_mask (kernels/accept_mask.hip) and K11 accept_swaps (kernels/accept_swap.hip). A
-// translation unit of its own, linked into libccmi.so only: the test emulation of Device has no acceptance kernels.
+// (kernels/accept.hip), K10 accept_mask (kernels/accept_mask.hip) and K11 accept_swaps (kernels/accept_swap.hip); and
+// Device::brokerStats, the launcher of K12 (kernels/broker_stats.hip), which shares their launch protocol. A translation
+// unit of its own, linked into libccmi.so only: the test emulation of Device has none of these kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -8,6 +9,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "ccmi.h"
 #include "device.h"
 #include "prof.h"
 
@@ -19,6 +21,13 @@ hipError_t launchAcceptMask(const DevTables& T, const DevProgram& prog, const Ma
                             unsigned long long* out, hipStream_t st);
 hipError_t launchAcceptSwaps(const DevTables& T, const DevProgram& prog, const SwapRow* rows, int64_t nSources,
                              const int32_t* cands, int64_t m, int8_t* out, hipStream_t st);
+hipError_t launchBrokerStatsRows(const BrokerRec* brokers, const BrokerStatic* meta, int B, ccmi_basic_stats* out, int D,
+                                 const double* dUtil, const double* dCap, const int32_t* dBroker,
+                                 ccmi_disk_stats* diskOut, hipStream_t st);
+hipError_t launchBrokerStatsHosts(const ccmi_basic_stats* rows, const int32_t* hOff, const int32_t* hBrk,
+                                  const int32_t* hIdx, int H, int B, ccmi_basic_stats* out, hipStream_t st);
+hipError_t launchBrokerStatsDisks(const DiskMember* members, int64_t E, const ReplicaRec* replicas, int R, int D,
+                                  ccmi_disk_stats* diskOut, hipStream_t st);
 
 namespace {
 void hipCheck(hipError_t e, const char* what) {
@@ -170,6 +179,96 @@ void Device::swapGridBatch(const DevProgram& prog, const SwapRow* rows, int64_t 
       hipCheck(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_), "hipEventElapsedTime");
       perf.acceptKernelMs += ms;
     }
+  }
+}
+
+void Device::uploadStatsStatic(const BrokerStatic* meta, int H, const int32_t* hOff, const int32_t* hBrk,
+                               const int32_t* hIdx, const int32_t* dBroker) {
+  CurrentDevice cur(ordinal_);
+  stopServer();
+  if (dStatMeta_) throw std::logic_error("uploadStatsStatic: once per session");
+  if (H < 1 || H > B_) throw std::logic_error("uploadStatsStatic: host count");
+  auto put = [&](auto** d, const auto* h, size_t n, const char* what) {
+    hipCheck(hipMalloc((void**)d, std::max<size_t>(1, n) * sizeof(**d)), what);
+    statsRowAllocs_.push_back(*d);
+    if (h && n) hipCheck(hipMemcpy(*d, h, n * sizeof(**d), hipMemcpyHostToDevice), what);
+  };
+  put(&dStatHOff_, hOff, (size_t)H + 1, "upload stats host offsets");
+  put(&dStatHBrk_, hBrk, (size_t)B_, "upload stats host brokers");
+  put(&dStatHIdx_, hIdx, (size_t)H, "upload stats host indices");
+  put(&dStatRows_, (const ccmi_basic_stats*)nullptr, (size_t)B_ + (size_t)H, "hipMalloc stats rows");
+  if (D_ > 0) {
+    put(&dStatDBroker_, dBroker, (size_t)D_, "upload stats disk brokers");
+    put(&dStatDisks_, (const ccmi_disk_stats*)nullptr, (size_t)D_, "hipMalloc disk stats rows");
+  }
+  statH_ = H;
+  put(&dStatMeta_, meta, (size_t)B_, "upload stats broker columns");  // last: statsStaticUploaded()
+}
+
+void Device::brokerStats(ccmi_basic_stats* brokers, ccmi_basic_stats* hosts, ccmi_disk_stats* disks,
+                         const DiskMember* members, int64_t nMembers, uint64_t memberVer) {
+  CurrentDevice cur(ordinal_);
+  PhaseScope ps(PH_DEV_SCAN);
+  stopServer();  // plain launches on the session stream, as maskBatch
+  if (!dStatMeta_) throw std::logic_error("brokerStats before uploadStatsStatic");
+  if (!brokers || nMembers < 0) throw std::logic_error("brokerStats: arguments");
+  const bool withDisks = disks && D_ > 0;
+  const hipStream_t st = (hipStream_t)st_;
+  // the rows the host changed since the last launch reach the tables first (prep, on the same stream)
+  if (!brows.empty() || !rrows.empty() || !prows.empty() || !tdeltas.empty()) {
+    const Staged g = packUpdates(0);
+    launchPrepFor(g, 0, false);
+  }
+  if (withDisks && memberVer != statMemberVer_) {
+    if ((size_t)nMembers > statMembersCap_) {
+      if (dStatMembers_) hipCheck(hipFree(dStatMembers_), "hipFree");
+      dStatMembers_ = nullptr;
+      statMembersCap_ = 0;
+      hipCheck(hipMalloc((void**)&dStatMembers_, (size_t)nMembers * sizeof(DiskMember)), "hipMalloc disk members");
+      statMembersCap_ = (size_t)nMembers;
+    }
+    if (nMembers)
+      hipCheck(hipMemcpyAsync(dStatMembers_, members, (size_t)nMembers * sizeof(DiskMember), hipMemcpyHostToDevice, st),
+               "upload disk members");
+    statMembers_ = nMembers;
+    statMemberVer_ = memberVer;
+  }
+  ccmi_basic_stats* dHosts = dStatRows_ + B_;
+  if (timing) (void)hipEventRecord((hipEvent_t)ev0_, st);
+  hipCheck(launchBrokerStatsRows(brokers_, dStatMeta_, B_, dStatRows_, withDisks ? D_ : 0, dDUtilIn_, dDCap_, dStatDBroker_,
+                                 dStatDisks_, st),
+           "broker_stats_rows");
+  int launches = 1;
+  if (hosts) {
+    hipCheck(launchBrokerStatsHosts(dStatRows_, dStatHOff_, dStatHBrk_, dStatHIdx_, statH_, B_, dHosts, st),
+             "broker_stats_hosts");
+    launches++;
+  }
+  if (withDisks && statMembers_ > 0) {
+    hipCheck(launchBrokerStatsDisks(dStatMembers_, statMembers_, replicas_, R_, D_, dStatDisks_, st), "broker_stats_disks");
+    launches++;
+  }
+  if (timing) (void)hipEventRecord((hipEvent_t)ev1_, st);
+  hipCheck(hipMemcpyAsync(brokers, dStatRows_, (size_t)B_ * sizeof(ccmi_basic_stats), hipMemcpyDeviceToHost, st),
+           "D2H broker stats");
+  if (hosts)
+    hipCheck(hipMemcpyAsync(hosts, dHosts, (size_t)statH_ * sizeof(ccmi_basic_stats), hipMemcpyDeviceToHost, st),
+             "D2H host stats");
+  if (withDisks)
+    hipCheck(hipMemcpyAsync(disks, dStatDisks_, (size_t)D_ * sizeof(ccmi_disk_stats), hipMemcpyDeviceToHost, st),
+             "D2H disk stats");
+  streamWait("broker_stats", kAcceptWaitSeconds);
+  perf.syncs++;
+  // ClusterModelStats' counters take it (a statistics read-back), not the acceptance ones: BrokerRec in, one row out per
+  // broker; a row in and out per host; two doubles in and a row out per disk, and a member entry plus the flags word
+  perf.statsLaunches += launches;
+  perf.statsBytes += (int64_t)B_ * (int64_t)(sizeof(BrokerRec) + sizeof(BrokerStatic) + sizeof(ccmi_basic_stats)) +
+                     (hosts ? (int64_t)B_ * (int64_t)sizeof(ccmi_basic_stats) + (int64_t)statH_ * 136 : 0) +
+                     (withDisks ? (int64_t)D_ * (16 + 4 + (int64_t)sizeof(ccmi_disk_stats)) + statMembers_ * 12 : 0);
+  if (timing) {
+    float ms = 0.f;
+    hipCheck(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_), "hipEventElapsedTime");
+    perf.statsKernelMs += ms;
   }
 }
 

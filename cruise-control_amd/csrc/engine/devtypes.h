@@ -247,6 +247,15 @@ struct alignas(16) SwapRow {
 static_assert(sizeof(SwapRow) == 16, "SwapRow is one 16-byte load");
 constexpr int64_t kMaxSwapCandidates = INT32_MAX - 63;  // candidates of one grid: the padded row still indexes as int32
 
+// ccmi_broker_stats (kernels/broker_stats.hip): what a broker's row takes from outside its BrokerRec (static: the
+// desc's host index and the ccmi_broker_state), and one member of a Disk._replicas.
+struct BrokerStatic {
+  int32_t host, state;
+};
+struct DiskMember {
+  int32_t replica, disk;
+};
+
 struct UpdateList {
   const BrokerRow* brows;
   const ReplicaRow* rrows;

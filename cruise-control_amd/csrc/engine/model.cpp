@@ -49,6 +49,8 @@ void Model::build(const ccmi_cluster_desc& d) {
   // broker's capacity and counts it alive (Host.java)
   sharedHosts = false;
   bHost.assign(B, 0);
+  bHostDesc.assign(B, 0);
+  for (int b = 0; b < B; ++b) bHostDesc[b] = d.broker_host ? d.broker_host[b] : b;
   {
     std::vector<int32_t> dense(d.broker_host ? (size_t)B : 0, -1), hostRack;
     H = 0;
@@ -382,6 +384,7 @@ void Model::diskAdd(int d, int r) {
   v.push_back(r);
   if (anyDemotedDisk) dReplicaSet[d].add(r, replicaHash(r));
   diskDirty = true;
+  diskMemberVer++;
 }
 void Model::diskRemove(int d, int r) {
   auto& v = dMembers[d];
@@ -403,6 +406,7 @@ void Model::diskRemove(int d, int r) {
   if (rDisk[r] == d) rDiskPos[r] = -1;
   if (anyDemotedDisk) dReplicaSet[d].remove(r, replicaHash(r));
   diskDirty = true;
+  diskMemberVer++;
 }
 void Model::relocateReplicaToDisk(int p, int b, int dst) {
   const int r = replicaOn(p, b);

@@ -143,6 +143,7 @@ class Model {
   // Disk._replicas entries left behind by inter-broker moves (Broker.removeReplica keeps the replica on its disk)
   int64_t diskGhosts = 0;
   bool diskDirty = true;                    // device copy of dUtil is stale
+  uint64_t diskMemberVer = 1;               // bumped whenever a Disk._replicas changes (diskAdd / diskRemove)
   int diskOf(int b, const std::string& logdir) const;
   double diskPct(int d) const { return dCap[d] > 0 ? dUtil[d] / dCap[d] : 1.0; }  // GoalUtils.diskUtilizationPercentage
   double avgDiskPct(int b) const;            // GoalUtils.averageDiskUtilizationPercentage
@@ -167,6 +168,7 @@ class Model {
   bool sharedHosts = false;
   int H = 0;
   std::vector<int32_t> bHost;                  // [B] dense host index
+  std::vector<int32_t> bHostDesc;              // [B] the desc's host index (broker_host[b], or b when that is NULL)
   std::vector<std::vector<int32_t>> hBrokers;  // [H] brokers of each host
   std::vector<LoadVec> hLoad;                  // [H] Host._load
   std::vector<double> hCap, hUtilC;            // [H][4] Host._hostCapacity, cached expectedUtilizationFor

@@ -19,6 +19,8 @@
  *                                 analyzer/goals/AbstractGoal.java:243-270 (legit and accepted brokers as bit masks)
  *   ccmi_swaps_acceptance_grid <- the candidate loop of AbstractGoal.maybeApplySwapAction
  *                                 analyzer/goals/AbstractGoal.java:287-338 (one code per replica pair)
+ *   ccmi_broker_stats          <- ClusterModel.brokerStats(KafkaCruiseControlConfig)  model/ClusterModel.java:1303-1309
+ *                                 (the load block of a rebalance response and of the load endpoint)
  *   ccmi_compute_cluster_stats <- ClusterModel.getClusterStats(BalancingConstraint, OptimizationOptions)
  *                                 model/ClusterModel.java:137-139 -> ClusterModelStats.populate :84-102
  *   ccmi_action_log_*          <- the ordered relocateReplica/relocateLeadership calls a goal makes
@@ -543,6 +545,57 @@ ccmi_status ccmi_session_apply(ccmi_session* s, const ccmi_action* actions, int6
 ccmi_status ccmi_last_failure_provision(const ccmi_session* s, ccmi_provision_response* out);
 ccmi_status ccmi_compute_cluster_stats(ccmi_session* s, const ccmi_balancing_constraint* constraint,
                                const ccmi_opt_options* options, ccmi_cluster_stats* out);
+
+/* servlet/response/stats/BasicStats.java of one broker (SingleBrokerStats) or one host (SingleHostStats). 128 bytes. */
+typedef struct ccmi_basic_stats {
+  double disk_mb, disk_pct, cpu_pct, leader_nw_in_rate, follower_nw_in_rate, nw_out_rate, pnw_out_rate;
+  double disk_capacity_mb, network_in_capacity, network_out_capacity, num_core;
+  int32_t replicas, leaders;
+  int32_t broker;   /* broker index; -1 in a host row */
+  int32_t state;    /* ccmi_broker_state; -1 in a host row */
+  int32_t host;     /* host index (desc.broker_host value, or the broker index when that is NULL) */
+  int32_t rack;
+  int32_t reserved[4]; /* 0 */
+} ccmi_basic_stats;
+/* model/DiskStats.java (Disk.diskStats, Disk.java:259-264) of one disk, desc disk order. */
+typedef struct ccmi_disk_stats {
+  double disk_mb, disk_pct;  /* both -1 for a disk with capacity <= 0 (the reference's null / "DEAD") */
+  double capacity;
+  int32_t num_replicas, num_leader_replicas, disk, broker;
+} ccmi_disk_stats;
+/* Additive at ABI v13 (the capability flag is the presence of the symbol). ClusterModel.brokerStats
+ * (ClusterModel.java:1303-1309) of the session's current model, computed on the device from the resident tables: what
+ * GoalOptimizer.java:442 takes before the first goal, OptimizerResult.java:111 after the last, and LoadMonitor.java:446
+ * for the load endpoint.
+ * brokers[b] is BasicStats(Broker, potentialBytesOutRate) (BasicStats.java:73-86) of broker b, every Math.max(x, 0.0)
+ * as Java evaluates it (NaN stays NaN, -0.0 becomes 0.0): disk_mb = max(broker.replicas().isEmpty() ? 0 :
+ * load.expectedUtilizationFor(DISK), 0); cpu_pct = max(100.0 * utilization(CPU) / capacityFor(CPU), 0) (a dead broker's
+ * capacity is -1, so 0); leader_nw_in_rate = max(leadershipLoadForNwResources().expectedUtilizationFor(NW_IN), 0);
+ * follower_nw_in_rate = max(utilization(NW_IN) - leader_nw_in_rate, 0); nw_out_rate = max(utilization(NW_OUT), 0);
+ * pnw_out_rate = max(potentialLeadershipLoadFor(b).expectedUtilizationFor(NW_OUT), 0); disk_capacity_mb,
+ * network_in_capacity, network_out_capacity = max(capacityFor(DISK | NW_IN | NW_OUT), 0); num_core = max(capacityFor(CPU)
+ * / 100, 0); disk_pct = disk_capacity_mb > 0 ? 100 * disk_mb / disk_capacity_mb : -1 (diskUtilPct, :94-96); replicas and
+ * leaders are broker.replicas().size() and broker.leaderReplicas().size(). The loads are the broker's own
+ * (broker.load()), never its host's, also when brokers share hosts. The reference's isEstimated flag
+ * (SingleBrokerStats) is not carried: the desc holds no capacity-estimation information.
+ * hosts (optional, room for B rows): one row per distinct host in ascending host index, each the
+ * SingleHostStats.addBasicStats sum (BasicStats.java:142-155) of the host's broker rows in ascending broker index
+ * (ClusterModel.brokers() is a TreeSet and the index order is id order), every field added in double in that order,
+ * disk_pct recomputed from the sums, rack the rack of the host's brokers, broker = state = -1; *num_hosts (optional)
+ * receives the row count. Ordering the hosts by name (the reference's ConcurrentSkipListMap) stays with the caller,
+ * which holds the names.
+ * disks (read only when the desc has num_disks > 0; optional): Disk.diskStats() of every disk in desc disk order.
+ * num_replicas is Disk._replicas.size() as the model keeps it — a replica an inter-broker move took away stays in its
+ * old disk's set (Broker.removeReplica does not touch disks) — num_leader_replicas its members with isLeader(),
+ * disk_mb Disk._utilization, disk_pct = disk_mb * 100.0 / capacity (DiskStats.java:54-56); disk_mb = disk_pct = -1 when
+ * capacity <= 0 (DiskStats' null utilization, "DEAD" in its JSON).
+ * The session is not changed. Valid on a fresh session (the stats before optimization), after any optimization and
+ * after ccmi_session_apply with no scan in between (the pending rows are sent first). A sharded session answers locally.
+ * No perf counter of the acceptance calls counts it. Errors: CCMI_E_INVALID for a NULL session or NULL brokers,
+ * CCMI_E_DEVICE for a device failure; on error the outputs are unspecified. */
+ccmi_status ccmi_broker_stats(ccmi_session* s, ccmi_basic_stats* brokers /* [B] */,
+                              ccmi_basic_stats* hosts /* [B] capacity, or NULL */, int32_t* num_hosts /* or NULL */,
+                              ccmi_disk_stats* disks /* [num_disks], or NULL */);
 
 int64_t ccmi_action_log_count(const ccmi_session* s);
 ccmi_status ccmi_action_log_copy(const ccmi_session* s, int64_t first, int64_t count, ccmi_action* out);
