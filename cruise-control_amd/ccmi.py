@@ -1289,6 +1289,30 @@ class ClusterModel:
                                                                    C.byref(out)))
         return ACCEPTANCE[out.value]
 
+    # ---- what the batched device calls share
+    def _not_exported(self, symbol: str, why: str) -> None:
+        raise UnsupportedOperationException(f"{self.lib.path} does not export {symbol}: {why}")
+
+    @staticmethod
+    def _int32_rows(np, rows, width: int, complaint: str):
+        """`rows` (tuples or an array) as a contiguous [k, width] int32 array: the rows are the C structs. `np` is the
+        caller's numpy (this module imports it only where it is used)."""
+        a = np.ascontiguousarray(rows if len(rows) else np.zeros((0, width)), dtype=np.int32)
+        if a.ndim != 2 or a.shape[1] != width:
+            raise IllegalArgumentException(complaint)
+        return a
+
+    def _goals_call(self, fn, names, *args) -> None:
+        """lib.check of fn(session, kinds of the goals `names`, their count, *args, first_invalid); what it raises
+        carries the index the call reported as `first_invalid`."""
+        kinds = (C.c_int32 * max(1, len(names)))(*map(GOAL_KINDS.__getitem__, names))
+        bad = C.c_int64(-1)
+        try:
+            self.lib.check(fn(self.handle, kinds, len(names), *args, C.byref(bad)))
+        except CruiseControlError as e:
+            e.first_invalid = bad.value
+            raise
+
     def actions_acceptance(self, goal_names, actions):
         """Goal.actionAcceptance of several optimized goals for a batch of actions in one device call
         (ccmi_actions_acceptance): a numpy int8 array [n, G] of ACCEPTANCE indices, cell [i, g] what
@@ -1298,25 +1322,13 @@ class ClusterModel:
         import numpy as np
 
         if not self.lib.has_actions_acceptance:
-            raise UnsupportedOperationException(
-                f"{self.lib.path} does not export ccmi_actions_acceptance: the batched call runs on the device only")
+            self._not_exported("ccmi_actions_acceptance", "the batched call runs on the device only")
         names = list(goal_names)
-        acts = np.ascontiguousarray(np.asarray(actions if len(actions) else np.zeros((0, 7)), dtype=np.int32))
-        if acts.ndim != 2 or acts.shape[1] != 7:
-            raise IllegalArgumentException("actions must be [n, 7]: the action-log layout")
-        n, G = acts.shape[0], len(names)
-        kinds = (C.c_int32 * max(1, G))(*[GOAL_KINDS[g] for g in names])
-        out = np.zeros((n, G), dtype=np.int8)
-        bad = C.c_int64(-1)
-        # ActionStruct is seven int32: the array rows are the structs
-        status = self.lib.lib.ccmi_actions_acceptance(
-            self.handle, kinds, G, C.cast(acts.ctypes.data, C.POINTER(ActionStruct)), n,
-            out.ctypes.data_as(C.POINTER(C.c_int8)), C.byref(bad))
-        try:
-            self.lib.check(status)
-        except CruiseControlError as e:
-            e.first_invalid = bad.value
-            raise
+        acts = self._int32_rows(np, actions, 7, "actions must be [n, 7]: the action-log layout")  # ActionStruct
+        n = acts.shape[0]
+        out = np.zeros((n, len(names)), dtype=np.int8)
+        self._goals_call(self.lib.lib.ccmi_actions_acceptance, names, C.cast(acts.ctypes.data, C.POINTER(ActionStruct)), n,
+                         out.ctypes.data_as(C.POINTER(C.c_int8)))
         return out
 
     def moves_acceptance_mask(self, goal_names, sources, packed=False):
@@ -1329,26 +1341,16 @@ class ClusterModel:
         import numpy as np
 
         if not self.lib.has_moves_acceptance_mask:
-            raise UnsupportedOperationException(
-                f"{self.lib.path} does not export ccmi_moves_acceptance_mask: the masks are computed on the device only")
+            self._not_exported("ccmi_moves_acceptance_mask", "the masks are computed on the device only")
         names = list(goal_names)
-        src = np.asarray(sources if len(sources) else np.zeros((0, 3)), dtype=np.int32)
-        if src.ndim != 2 or src.shape[1] != 3:
-            raise IllegalArgumentException("sources must be [n, 3]: type, partition, source broker")
-        n, G, B = src.shape[0], len(names), self.desc.num_brokers
-        rows = np.zeros((n, 4), dtype=np.int32)  # ccmi_move_source is four int32: the array rows are the structs
+        src = self._int32_rows(np, sources, 3, "sources must be [n, 3]: type, partition, source broker")
+        n, B = src.shape[0], self.desc.num_brokers
+        rows = np.zeros((n, 4), dtype=np.int32)  # ccmi_move_source is four int32: three and a reserved one
         rows[:, :3] = src
-        kinds = (C.c_int32 * max(1, G))(*[GOAL_KINDS[g] for g in names])
         W = (B + 63) // 64
         words = np.zeros((n, W), dtype=np.uint64)
-        bad = C.c_int64(-1)
-        status = self.lib.lib.ccmi_moves_acceptance_mask(self.handle, kinds, G, rows.ctypes.data, n,
-                                                         words.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(bad))
-        try:
-            self.lib.check(status)
-        except CruiseControlError as e:
-            e.first_invalid = bad.value
-            raise
+        self._goals_call(self.lib.lib.ccmi_moves_acceptance_mask, names, rows.ctypes.data, n,
+                         words.ctypes.data_as(C.POINTER(C.c_uint64)))
         if packed:
             return words
         bits = np.unpackbits(words.view(np.uint8).reshape(n, W * 8), axis=1, bitorder="little")
@@ -1364,28 +1366,15 @@ class ClusterModel:
         import numpy as np
 
         if not self.lib.has_swaps_acceptance_grid:
-            raise UnsupportedOperationException(
-                f"{self.lib.path} does not export ccmi_swaps_acceptance_grid: the grid is computed on the device only")
+            self._not_exported("ccmi_swaps_acceptance_grid", "the grid is computed on the device only")
         names = list(goal_names)
-
-        def replicas(what, rows):  # ccmi_swap_replica is two int32: the array rows are the structs
-            a = np.ascontiguousarray(rows if len(rows) else np.zeros((0, 2)), dtype=np.int32)
-            if a.ndim != 2 or a.shape[1] != 2:
-                raise IllegalArgumentException(f"{what} must be [k, 2]: partition, broker")
-            return a
-
-        src, cand = replicas("sources", sources), replicas("candidates", candidates)
-        n, m, G = src.shape[0], cand.shape[0], len(names)
-        kinds = (C.c_int32 * max(1, G))(*[GOAL_KINDS[g] for g in names])
+        # ccmi_swap_replica is two int32
+        src = self._int32_rows(np, sources, 2, "sources must be [k, 2]: partition, broker")
+        cand = self._int32_rows(np, candidates, 2, "candidates must be [k, 2]: partition, broker")
+        n, m = src.shape[0], cand.shape[0]
         codes = np.zeros((n, m), dtype=np.int8)
-        bad = C.c_int64(-1)
-        status = self.lib.lib.ccmi_swaps_acceptance_grid(self.handle, kinds, G, src.ctypes.data, n, cand.ctypes.data, m,
-                                                         codes.ctypes.data_as(C.POINTER(C.c_int8)), C.byref(bad))
-        try:
-            self.lib.check(status)
-        except CruiseControlError as e:
-            e.first_invalid = bad.value
-            raise
+        self._goals_call(self.lib.lib.ccmi_swaps_acceptance_grid, names, src.ctypes.data, n, cand.ctypes.data, m,
+                         codes.ctypes.data_as(C.POINTER(C.c_int8)))
         return codes
 
     def stats_names(self):
@@ -1402,8 +1391,7 @@ class ClusterModel:
         import numpy as np
 
         if not self.lib.has_broker_stats:
-            raise UnsupportedOperationException(
-                f"{self.lib.path} does not export ccmi_broker_stats: the stats are computed on the device only")
+            self._not_exported("ccmi_broker_stats", "the stats are computed on the device only")
         B, D = self.desc.num_brokers, self.desc.num_disks
         brokers = np.zeros(B, dtype=np.dtype(BasicStatsStruct))
         hosts = np.zeros(B, dtype=np.dtype(BasicStatsStruct))

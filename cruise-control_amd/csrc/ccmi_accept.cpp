@@ -17,6 +17,94 @@
 namespace {
 
 using ccmi::AcceptRow;
+using ccmi::SourceRow;
+
+// ---- the arguments of a call, in the order every entry point refuses them
+void checkArguments(const ccmi_session* s, bool negativeCount, bool nullArgument) {
+  if (!s) throw std::invalid_argument("null session");
+  if (negativeCount) throw std::invalid_argument("negative count");
+  if (nullArgument) throw std::invalid_argument("null argument");
+}
+
+// ---- the goals of a call
+struct GoalList {
+  std::vector<const ccmi::GoalImpl*> goals;    // one per kind, in the caller's order
+  std::vector<int> devCols;                    // the indices of those the device answers (every one but intra-broker goals)
+  const ccmi::GoalImpl* terminal = nullptr;    // the first of the device's goals after which no goal may run
+};
+
+// Each kind is the session's latest optimization of it (ccmi_action_acceptance_by_kind); a kind named twice is
+// evaluated twice. Intra-broker goals read the disk tables, which the scan kernels do not hold: with `noIntra` null
+// they stay in the list for the host to answer, else they are refused as having no `noIntra`.
+GoalList resolveGoals(const ccmi::Engine& e, const int32_t* kinds, int32_t n, const char* noIntra) {
+  GoalList gl;
+  for (int g = 0; g < n; ++g) {
+    const bool intra = ccmi::isIntraGoalKind(kinds[g]);
+    if (intra && noIntra)
+      throw ccmi::Unsupported("goal kind " + std::to_string(kinds[g]) +
+                              " is an intra-broker goal: it shares no chain with inter-broker goals and has no " +
+                              noIntra + "; ccmi_actions_acceptance answers its cells on the host");
+    const ccmi::GoalImpl* goal = e.optimizedOfKind(kinds[g]);
+    if (!goal) throw std::invalid_argument("the session has not optimized goal kind " + std::to_string(kinds[g]));
+    gl.goals.push_back(goal);
+    if (intra) continue;
+    gl.devCols.push_back(g);
+    if (!gl.terminal && goal->terminal) gl.terminal = goal;
+  }
+  return gl;
+}
+
+[[noreturn]] void throwTerminal(const GoalList& gl) {
+  throw ccmi::StateError("No goal should be executed after " + gl.terminal->name);
+}
+
+// ---- the rows of a call: indices are checked against the model first (the kernels trust their rows)
+// (the throw stays out of line so that the checks, which run once or twice per row, are inlined into the row loops)
+[[noreturn]] __attribute__((noinline)) void invalid(const char* what) { throw std::invalid_argument(what); }
+inline void checkPartition(const ccmi::Model& m, int p) {
+  if (p < 0 || p >= m.P) invalid("partition out of range");
+}
+inline void checkBroker(const ccmi::Model& m, int b) {
+  if (b < 0 || b >= m.B) invalid("broker out of range");
+}
+// the replica of partition p on broker b; `none` is the caller's word for a broker that holds none
+inline int replicaOf(const ccmi::Model& m, int p, int b, const char* none) {
+  checkPartition(m, p);
+  checkBroker(m, b);
+  const int r = m.replicaOn(p, b);
+  if (r < 0) invalid(none);
+  return r;
+}
+// f() for the caller's row `index`: an invalid_argument on its way out, and nothing else, makes it *first_invalid
+template <class F>
+auto atIndex(int64_t* first_invalid, int64_t index, F f) {
+  try {
+    return f();
+  } catch (std::invalid_argument&) {
+    if (first_invalid) *first_invalid = index;
+    throw;
+  }
+}
+
+// ---- the device programs of a call
+// The device goals [c0, c0 + G) of the list. Every slot is an actionAcceptance column: no slot is the goal being
+// optimized. The kernels gather whole records, so the scan programs' operand mask and candidate filters stay clear.
+ccmi::DevProgram programOf(const GoalList& gl, size_t c0, int G, int action) {
+  ccmi::DevProgram prog;
+  std::memset(&prog, 0, sizeof(prog));
+  prog.nGoals = G;
+  prog.action = action;
+  for (int g = 0; g < G; ++g) prog.goals[g] = gl.goals[gl.devCols[c0 + g]]->dg;
+  return prog;
+}
+// run(program, c0, G) for one device program per kMaxGoals device goals; `atLeastOne`: one even without goals
+template <class Run>
+void forEachProgram(const GoalList& gl, int action, bool atLeastOne, Run run) {
+  for (size_t c0 = 0; (atLeastOne && c0 == 0) || c0 < gl.devCols.size(); c0 += ccmi::kMaxGoals) {
+    const int G = (int)std::min<size_t>(ccmi::kMaxGoals, gl.devCols.size() - c0);
+    run(programOf(gl, c0, G, action), c0, G);
+  }
+}
 
 // The batch in device order: moves and leadership moves first, swaps after them, each segment padded to whole
 // wavefronts with copies of its last row (index -1: no caller row) so a wavefront runs one dispatch function.
@@ -33,27 +121,18 @@ void padToWave(Resolved& r) {
   }
 }
 
-// The row of action i as Engine::acceptance resolves it; throws what the single call throws. Indices are checked
-// against the model first (the kernel trusts its rows).
+// The row of action i as Engine::acceptance resolves it; throws what the single call throws.
 AcceptRow resolve(const ccmi::Model& m, const ccmi_action& a) {
   if (a.type != CCMI_INTER_BROKER_REPLICA_MOVEMENT && a.type != CCMI_LEADERSHIP_MOVEMENT &&
       a.type != CCMI_INTER_BROKER_REPLICA_SWAP)
     throw std::invalid_argument("Unsupported balancing action " + std::to_string(a.type) + " is provided.");
-  auto partition = [&](int p) {
-    if (p < 0 || p >= m.P) throw std::invalid_argument("partition out of range");
-  };
-  auto broker = [&](int b) {
-    if (b < 0 || b >= m.B) throw std::invalid_argument("broker out of range");
-  };
-  partition(a.partition);
-  broker(a.source_broker);
-  broker(a.destination_broker);
-  const int sr = m.replicaOn(a.partition, a.source_broker);
-  if (sr < 0) throw std::invalid_argument("no replica of the partition on the source broker");
+  checkPartition(m, a.partition);
+  checkBroker(m, a.source_broker);
+  checkBroker(m, a.destination_broker);  // before the source's replica is looked up
+  const int sr = replicaOf(m, a.partition, a.source_broker, "no replica of the partition on the source broker");
   if (a.type == CCMI_INTER_BROKER_REPLICA_SWAP) {
-    partition(a.destination_partition);
-    const int dr = m.replicaOn(a.destination_partition, a.destination_broker);
-    if (dr < 0) throw std::invalid_argument("no replica of the destination partition on the destination broker");
+    const int dr = replicaOf(m, a.destination_partition, a.destination_broker,
+                             "no replica of the destination partition on the destination broker");
     return AcceptRow{sr, dr, a.destination_broker, ccmi::DA_SWAP};
   }
   return AcceptRow{sr, -1, a.destination_broker,
@@ -67,50 +146,32 @@ extern "C" ccmi_status ccmi_actions_acceptance(ccmi_session* s, const int32_t* g
                                                int64_t* first_invalid) {
   if (first_invalid) *first_invalid = -1;
   return guarded([&] {
-    if (!s) throw std::invalid_argument("null session");
-    if (num_goals < 0 || n < 0) throw std::invalid_argument("negative count");
-    if ((num_goals > 0 && !goal_kinds) || (n > 0 && !actions) || (n > 0 && num_goals > 0 && !acceptance))
-      throw std::invalid_argument("null argument");
+    checkArguments(s, num_goals < 0 || n < 0,
+                   (num_goals > 0 && !goal_kinds) || (n > 0 && !actions) || (n > 0 && num_goals > 0 && !acceptance));
     ccmi::Engine& e = *s->engine;
-    // each kind is the session's latest optimization of it (ccmi_action_acceptance_by_kind)
-    std::vector<const ccmi::GoalImpl*> goals(num_goals);
-    for (int g = 0; g < num_goals; ++g) {
-      goals[g] = e.optimizedOfKind(goal_kinds[g]);
-      if (!goals[g])
-        throw std::invalid_argument("the session has not optimized goal kind " + std::to_string(goal_kinds[g]));
-    }
+    // columns of intra-broker goals are the host's
+    const GoalList gl = resolveGoals(e, goal_kinds, num_goals, nullptr);
     if (n == 0 || num_goals == 0) return CCMI_OK;
     const ccmi::ThreadPin pin(s->deviceOrdinal);  // restored when the call returns
-    // columns of intra-broker goals are the host's (they read the disk tables the scan kernels do not hold)
-    std::vector<int> devCols;
-    const ccmi::GoalImpl* terminal = nullptr;
-    for (int g = 0; g < num_goals; ++g)
-      if (!ccmi::isIntraGoalKind(goals[g]->kind)) {
-        devCols.push_back(g);
-        if (!terminal && goals[g]->terminal) terminal = goals[g];
-      }
     // every error of the single calls, before anything runs on the device
     Resolved moves, swaps;
     for (int64_t i = 0; i < n; ++i) {
       const ccmi_action& a = actions[i];
-      try {
+      atIndex(first_invalid, i, [&] {
         for (int g = 0; g < num_goals; ++g)
-          if (ccmi::isIntraGoalKind(goals[g]->kind))
-            acceptance[i * num_goals + g] = (int8_t)ccmi::intraAcceptance(*goals[g], e, a);
-        if (devCols.empty()) continue;
+          if (ccmi::isIntraGoalKind(gl.goals[g]->kind))
+            acceptance[i * num_goals + g] = (int8_t)ccmi::intraAcceptance(*gl.goals[g], e, a);
+        if (gl.devCols.empty()) return;
         if (a.type == CCMI_INTRA_BROKER_REPLICA_MOVEMENT || a.type == CCMI_INTRA_BROKER_REPLICA_SWAP)
           throw std::invalid_argument("Unsupported balancing action " + std::to_string(a.type) + " is provided.");
-        if (terminal) throw ccmi::StateError("No goal should be executed after " + terminal->name);
+        if (gl.terminal) throwTerminal(gl);
         const AcceptRow row = resolve(s->model, a);
         Resolved& seg = row.action == ccmi::DA_SWAP ? swaps : moves;
         seg.rows.push_back(row);
         seg.index.push_back(i);
-      } catch (std::invalid_argument&) {
-        if (first_invalid) *first_invalid = i;
-        throw;
-      }
+      });
     }
-    if (devCols.empty()) return CCMI_OK;
+    if (gl.devCols.empty()) return CCMI_OK;
     padToWave(moves);
     padToWave(swaps);
     Resolved all = std::move(moves);
@@ -121,24 +182,16 @@ extern "C" ccmi_status ccmi_actions_acceptance(ccmi_session* s, const int32_t* g
 
     s->model.flushToDevice();  // the rows the host changed since the last launch (ccmi_session_apply, a goal's moves)
     std::vector<int8_t> cells;
-    for (size_t c0 = 0; c0 < devCols.size(); c0 += ccmi::kMaxGoals) {
-      const int G = (int)std::min<size_t>(ccmi::kMaxGoals, devCols.size() - c0);
-      // every slot is an actionAcceptance column: no slot is the goal being optimized. The kernel gathers whole
-      // records, so the scan programs' operand mask and candidate filters stay clear.
-      ccmi::DevProgram prog;
-      std::memset(&prog, 0, sizeof(prog));
-      prog.nGoals = G;
-      prog.action = ccmi::DA_MOVE;
-      for (int g = 0; g < G; ++g) prog.goals[g] = goals[devCols[c0 + g]]->dg;
+    forEachProgram(gl, ccmi::DA_MOVE, false, [&](const ccmi::DevProgram& prog, size_t c0, int G) {
       cells.resize((size_t)nRows * G);
       s->device->acceptBatch(prog, all.rows.data(), nRows, all.nMoveRows, cells.data());
       s->device->perf.acceptCells += n * G;
       for (int64_t r = 0; r < nRows; ++r) {  // back to the caller's order
         const int64_t i = all.index[r];
         if (i < 0) continue;
-        for (int g = 0; g < G; ++g) acceptance[i * num_goals + devCols[c0 + g]] = cells[(size_t)r * G + g];
+        for (int g = 0; g < G; ++g) acceptance[i * num_goals + gl.devCols[c0 + g]] = cells[(size_t)r * G + g];
       }
-    }
+    });
     return CCMI_OK;
   });
 }
@@ -148,58 +201,30 @@ extern "C" ccmi_status ccmi_moves_acceptance_mask(ccmi_session* s, const int32_t
                                                   int64_t* first_invalid) {
   if (first_invalid) *first_invalid = -1;
   return guarded([&] {
-    if (!s) throw std::invalid_argument("null session");
-    if (num_goals < 0 || n < 0) throw std::invalid_argument("negative count");
-    if ((num_goals > 0 && !goal_kinds) || (n > 0 && (!sources || !mask))) throw std::invalid_argument("null argument");
-    ccmi::Engine& e = *s->engine;
-    // each kind is the session's latest optimization of it; a kind named twice is evaluated twice (a conjunction)
-    std::vector<const ccmi::GoalImpl*> goals;
-    const ccmi::GoalImpl* terminal = nullptr;
-    for (int g = 0; g < num_goals; ++g) {
-      if (ccmi::isIntraGoalKind(goal_kinds[g]))
-        throw ccmi::Unsupported("goal kind " + std::to_string(goal_kinds[g]) +
-                                " is an intra-broker goal: it shares no chain with inter-broker goals and has no "
-                                "destination-broker mask; ccmi_actions_acceptance answers its cells on the host");
-      const ccmi::GoalImpl* goal = e.optimizedOfKind(goal_kinds[g]);
-      if (!goal) throw std::invalid_argument("the session has not optimized goal kind " + std::to_string(goal_kinds[g]));
-      if (!terminal && goal->terminal) terminal = goal;
-      goals.push_back(goal);
-    }
+    checkArguments(s, num_goals < 0 || n < 0, (num_goals > 0 && !goal_kinds) || (n > 0 && (!sources || !mask)));
+    const GoalList gl = resolveGoals(*s->engine, goal_kinds, num_goals, "destination-broker mask");  // a conjunction
     if (n == 0) return CCMI_OK;
-    if (terminal) throw ccmi::StateError("No goal should be executed after " + terminal->name);
-    // every source against the model before anything runs on the device (the kernel trusts its rows)
+    if (gl.terminal) throwTerminal(gl);
+    // every source against the model before anything runs on the device
     const ccmi::Model& m = s->model;
-    std::vector<ccmi::MaskRow> rows((size_t)n);
+    std::vector<SourceRow> rows((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
       const ccmi_move_source& a = sources[i];
-      try {
+      rows[(size_t)i] = atIndex(first_invalid, i, [&] {
         if (a.type != CCMI_INTER_BROKER_REPLICA_MOVEMENT && a.type != CCMI_LEADERSHIP_MOVEMENT)
           throw std::invalid_argument("a move source is a replica movement or a leadership movement, not action type " +
                                       std::to_string(a.type));
-        if (a.partition < 0 || a.partition >= m.P) throw std::invalid_argument("partition out of range");
-        if (a.source_broker < 0 || a.source_broker >= m.B) throw std::invalid_argument("broker out of range");
-        const int sr = m.replicaOn(a.partition, a.source_broker);
-        if (sr < 0) throw std::invalid_argument("no replica of the partition on the source broker");
-        rows[(size_t)i] = ccmi::MaskRow{sr, a.partition, a.source_broker,
-                                        a.type == CCMI_LEADERSHIP_MOVEMENT ? ccmi::DA_LEADERSHIP : ccmi::DA_MOVE};
-      } catch (std::invalid_argument&) {
-        if (first_invalid) *first_invalid = i;
-        throw;
-      }
+        const int sr = replicaOf(m, a.partition, a.source_broker, "no replica of the partition on the source broker");
+        return SourceRow{sr, a.partition, a.source_broker,
+                         a.type == CCMI_LEADERSHIP_MOVEMENT ? ccmi::DA_LEADERSHIP : ccmi::DA_MOVE};
+      });
     }
     const ccmi::ThreadPin pin(s->deviceOrdinal);  // restored when the call returns
     s->model.flushToDevice();  // the rows the host changed since the last launch (ccmi_session_apply, a goal's moves)
     const size_t words = (size_t)n * (size_t)s->device->maskWords();
     std::vector<uint64_t> part;
-    // one device program per kMaxGoals goals (at least one: without goals, the legit mask); the masks are ANDed
-    for (size_t c0 = 0; c0 == 0 || c0 < goals.size(); c0 += ccmi::kMaxGoals) {
-      const int G = (int)std::min<size_t>(ccmi::kMaxGoals, goals.size() - c0);
-      // every slot is an actionAcceptance column, as in ccmi_actions_acceptance
-      ccmi::DevProgram prog;
-      std::memset(&prog, 0, sizeof(prog));
-      prog.nGoals = G;
-      prog.action = ccmi::DA_MOVE;
-      for (int g = 0; g < G; ++g) prog.goals[g] = goals[c0 + g]->dg;
+    // without goals, the legit mask; the programs' masks are ANDed
+    forEachProgram(gl, ccmi::DA_MOVE, true, [&](const ccmi::DevProgram& prog, size_t c0, int) {
       if (c0 == 0) {
         s->device->maskBatch(prog, rows.data(), n, mask);
       } else {
@@ -207,7 +232,7 @@ extern "C" ccmi_status ccmi_moves_acceptance_mask(ccmi_session* s, const int32_t
         s->device->maskBatch(prog, rows.data(), n, part.data());
         for (size_t w = 0; w < words; ++w) mask[w] &= part[w];
       }
-    }
+    });
     // the cells the masks stand for, early exits included
     s->device->perf.acceptCells += n * (int64_t)m.B * num_goals;
     return CCMI_OK;
@@ -220,61 +245,31 @@ extern "C" ccmi_status ccmi_swaps_acceptance_grid(ccmi_session* s, const int32_t
                                                   int64_t* first_invalid) {
   if (first_invalid) *first_invalid = -1;
   return guarded([&] {
-    if (!s) throw std::invalid_argument("null session");
-    if (num_goals < 0 || n < 0 || m < 0) throw std::invalid_argument("negative count");
-    if ((num_goals > 0 && !goal_kinds) || (n > 0 && !sources) || (m > 0 && !candidates) || (n > 0 && m > 0 && !codes))
-      throw std::invalid_argument("null argument");
-    ccmi::Engine& e = *s->engine;
-    // each kind is the session's latest optimization of it, in the caller's order: the code is the first verdict that
-    // is not ACCEPT
-    std::vector<const ccmi::GoalImpl*> goals;
-    const ccmi::GoalImpl* terminal = nullptr;
-    for (int g = 0; g < num_goals; ++g) {
-      if (ccmi::isIntraGoalKind(goal_kinds[g]))
-        throw ccmi::Unsupported("goal kind " + std::to_string(goal_kinds[g]) +
-                                " is an intra-broker goal: it shares no chain with inter-broker goals and has no "
-                                "swap grid; ccmi_actions_acceptance answers its cells on the host");
-      const ccmi::GoalImpl* goal = e.optimizedOfKind(goal_kinds[g]);
-      if (!goal) throw std::invalid_argument("the session has not optimized goal kind " + std::to_string(goal_kinds[g]));
-      if (!terminal && goal->terminal) terminal = goal;
-      goals.push_back(goal);
-    }
+    checkArguments(s, num_goals < 0 || n < 0 || m < 0,
+                   (num_goals > 0 && !goal_kinds) || (n > 0 && !sources) || (m > 0 && !candidates) ||
+                       (n > 0 && m > 0 && !codes));
+    // in the caller's order: the code is the first verdict that is not ACCEPT
+    const GoalList gl = resolveGoals(*s->engine, goal_kinds, num_goals, "swap grid");
     if (n == 0 || m == 0) return CCMI_OK;
-    if (terminal) throw ccmi::StateError("No goal should be executed after " + terminal->name);
-    // every replica against the model before anything runs on the device (the kernel trusts its rows): n + m
-    // resolutions, sources first
+    if (gl.terminal) throwTerminal(gl);
+    // every replica against the model before anything runs on the device: n + m resolutions, sources first
     const ccmi::Model& md = s->model;
     auto resolve = [&](const ccmi_swap_replica& a, int64_t index) {
-      try {
-        if (a.partition < 0 || a.partition >= md.P) throw std::invalid_argument("partition out of range");
-        if (a.broker < 0 || a.broker >= md.B) throw std::invalid_argument("broker out of range");
-        const int r = md.replicaOn(a.partition, a.broker);
-        if (r < 0) throw std::invalid_argument("no replica of the partition on the broker");
-        return r;
-      } catch (std::invalid_argument&) {
-        if (first_invalid) *first_invalid = index;
-        throw;
-      }
+      return atIndex(first_invalid, index,
+                     [&] { return replicaOf(md, a.partition, a.broker, "no replica of the partition on the broker"); });
     };
-    std::vector<ccmi::SwapRow> rows((size_t)n);
+    std::vector<SourceRow> rows((size_t)n);
     for (int64_t i = 0; i < n; ++i)
-      rows[(size_t)i] = ccmi::SwapRow{resolve(sources[i], i), sources[i].partition, sources[i].broker, ccmi::DA_SWAP};
+      rows[(size_t)i] = SourceRow{resolve(sources[i], i), sources[i].partition, sources[i].broker, ccmi::DA_SWAP};
     std::vector<int32_t> cands((size_t)m);
     for (int64_t j = 0; j < m; ++j) cands[(size_t)j] = resolve(candidates[j], n + j);
     const ccmi::ThreadPin pin(s->deviceOrdinal);  // restored when the call returns
     s->model.flushToDevice();  // the rows the host changed since the last launch (ccmi_session_apply, a goal's moves)
     const size_t cells = (size_t)n * (size_t)m;
     std::vector<int8_t> part;
-    // one device program per kMaxGoals goals (at least one: without goals, the legitimacy grid). Codes 3 and 4 are the
-    // same in every program; a cell still at 0 takes the next program's code
-    for (size_t c0 = 0; c0 == 0 || c0 < goals.size(); c0 += ccmi::kMaxGoals) {
-      const int G = (int)std::min<size_t>(ccmi::kMaxGoals, goals.size() - c0);
-      // every slot is an actionAcceptance column, as in ccmi_actions_acceptance
-      ccmi::DevProgram prog;
-      std::memset(&prog, 0, sizeof(prog));
-      prog.nGoals = G;
-      prog.action = ccmi::DA_SWAP;
-      for (int g = 0; g < G; ++g) prog.goals[g] = goals[c0 + g]->dg;
+    // without goals, the legitimacy grid. Codes 3 and 4 are the same in every program; a cell still at 0 takes the next
+    // program's code
+    forEachProgram(gl, ccmi::DA_SWAP, true, [&](const ccmi::DevProgram& prog, size_t c0, int) {
       if (c0 == 0) {
         s->device->swapGridBatch(prog, rows.data(), n, cands.data(), m, codes);
       } else {
@@ -283,7 +278,7 @@ extern "C" ccmi_status ccmi_swaps_acceptance_grid(ccmi_session* s, const int32_t
         for (size_t c = 0; c < cells; ++c)
           if (codes[c] == 0) codes[c] = part[c];
       }
-    }
+    });
     // the cells the codes stand for, early exits included
     s->device->perf.acceptCells += n * m * num_goals;
     return CCMI_OK;

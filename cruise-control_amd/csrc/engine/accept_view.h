@@ -40,7 +40,7 @@ struct AcceptView {
   // A move or leadership move of replica a.sr (of partition a.p, on broker a.src) to broker dst: one replica and one
   // partition, so the second of each is the first. Every load but the destination's depends on the row alone — in K10 on
   // wave-uniform values, which the compiler keeps in scalar registers.
-  __device__ __forceinline__ void loadMove(const DevTables& T, const MaskRow& a, int dst) {
+  __device__ __forceinline__ void loadMove(const DevTables& T, const SourceRow& a, int dst) {
     t = T;
     r0 = r1 = a.sr;
     p0 = a.p;
@@ -55,7 +55,7 @@ struct AcceptView {
   // A swap of replica a.sr (of partition a.p, on broker a.src) with replica `cand`, whose broker is the destination. The
   // first of each record depends on the row alone (in K11 wave-uniform, scalar registers); the second hangs off the
   // candidate: its ReplicaRec, then that replica's partition and broker.
-  __device__ __forceinline__ void loadSwap(const DevTables& T, const SwapRow& a, int cand) {
+  __device__ __forceinline__ void loadSwap(const DevTables& T, const SourceRow& a, int cand) {
     t = T;
     r0 = a.sr;
     r1 = cand;

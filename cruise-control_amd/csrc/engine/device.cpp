@@ -1,5 +1,6 @@
 // Device tables, staging and launch protocol (see device.h).
 #include "device.h"
+#include "hip_check.h"
 #include "intra.h"
 #include "hostpool.h"
 #include "prof.h"
@@ -74,31 +75,12 @@ hipError_t launchStatsDisks(const int32_t* bDiskOff, const int32_t* bDisks, cons
                             const double* dUtil, const uint8_t* bAlive, int B, double balance, DiskStatsOut* out,
                             hipStream_t st);
 
-static void hipCheck(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
-}
-
 template <class T>
 static void dalloc(T** p, size_t n) {
   hipCheck(hipMalloc((void**)p, (n ? n : 1) * sizeof(T)), "hipMalloc");
 }
 
 static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-// HIP's current device is per host thread and starts at 0; a session may run on a thread other than the one that
-// created it (the reference's precompute pool, bench.py --requests-per-gpu). Every public entry point that touches
-// the device makes the session's ordinal current for its duration and restores the caller's device afterwards.
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int ordinal) {
-    hipCheck(hipGetDevice(&prev), "hipGetDevice");
-    if (prev != ordinal) hipCheck(hipSetDevice(ordinal), "hipSetDevice");
-    else prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 bool deviceLocalCpuList(int ordinal, std::string& out) {
   char bus[64] = {0};

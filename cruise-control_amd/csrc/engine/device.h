@@ -263,7 +263,7 @@ class Device {
   // actionAcceptance column) ACCEPTs: out[source * W + (b >> 6)] bit (b & 63), W = maskWords(); bits of brokers >= B are
   // 0. The pending row updates go to the tables first; one launch and one stream sync per CCMI_MASK_CHUNK_SOURCES sources.
   // Not in the test emulation.
-  void maskBatch(const DevProgram& prog, const MaskRow* rows, int64_t nSources, uint64_t* out);
+  void maskBatch(const DevProgram& prog, const SourceRow* rows, int64_t nSources, uint64_t* out);
   int maskWords() const { return (B_ + 63) / 64; }
   // K11 (kernels/accept_swap.hip, device_accept.cpp): the swap code of every (source, candidate replica) pair of
   // nSources resolved sources and m candidate replica ids (1 <= m <= kMaxSwapCandidates) under `prog` (goals[0, nGoals),
@@ -271,7 +271,7 @@ class Device {
   // legitMove fails, else the first non-ACCEPT verdict in goal order, else 0. The pending row updates go to the tables
   // first; one launch and one stream sync per max(1, min(65535, CCMI_SWAP_CHUNK_CELLS / pitch)) sources, pitch = m
   // rounded up to 64. Not in the test emulation.
-  void swapGridBatch(const DevProgram& prog, const SwapRow* rows, int64_t nSources, const int32_t* cands, int64_t m,
+  void swapGridBatch(const DevProgram& prog, const SourceRow* rows, int64_t nSources, const int32_t* cands, int64_t m,
                      int8_t* out);
   // K12 (kernels/broker_stats.hip, device_accept.cpp): ClusterModel.brokerStats from the resident tables.
   // uploadStatsStatic once per session: every broker's {desc host index, state}, the hosts' brokers as CSR (H hosts in
@@ -412,6 +412,18 @@ class Device {
   int8_t* dAccept_ = nullptr;
   size_t acceptCap_ = 0;
   void ensureAccept(size_t bytes);
+  // device_accept.cpp, its only user. PlainLaunch: the scope of a call that launches on the session stream with no
+  // server resident. acceptChunk: one chunk of acceptBatch / maskBatch / swapGridBatch — fill(p) writes the req-byte
+  // request behind the staged row updates, prep takes both to HBM, launch(stream) starts the kernel and its outBytes of
+  // dAccept_ come back to dst; one stream sync, one accept launch counted. timedLaunch / addKernelMs: the HIP-event
+  // pair around a call's kernels and, after the stream wait, their time (kernel timing on).
+  struct PlainLaunch;
+  template <class Fill, class Launch>
+  void acceptChunk(size_t req, Fill fill, size_t outBytes, Launch launch, void* dst, const char* kernel,
+                   const char* copy);
+  template <class Launch>
+  void timedLaunch(Launch launch);
+  void addKernelMs(double& total);
   int acceptChunkRows_ = 1 << 17;  // action rows per launch (CCMI_ACCEPT_CHUNK_ROWS, read at session create)
   int maskChunkSources_ = 4096;    // sources per launch (CCMI_MASK_CHUNK_SOURCES, read at session create)
   std::vector<int8_t> swapHost_;      // one chunk's pitched codes on the host, before the pitch is removed

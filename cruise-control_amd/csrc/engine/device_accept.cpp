@@ -1,7 +1,8 @@
 // Device::acceptBatch, Device::maskBatch and Device::swapGridBatch (device.h): the launchers of K9 accept_actions
-// (kernels/accept.hip), K10 accept_mask (kernels/accept_mask.hip) and K11 accept_swaps (kernels/accept_swap.hip); and
-// Device::brokerStats, the launcher of K12 (kernels/broker_stats.hip), which shares their launch protocol. A translation
-// unit of its own, linked into libccmi.so only: the test emulation of Device has none of these kernels.
+// (kernels/accept.hip), K10 accept_mask (kernels/accept_mask.hip) and K11 accept_swaps (kernels/accept_swap.hip), which
+// share one chunk protocol (Device::acceptChunk); and Device::brokerStats, the launcher of K12
+// (kernels/broker_stats.hip), which shares its scope and timing. A translation unit of its own, linked into libccmi.so
+// only: the test emulation of Device has none of these kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,15 +12,16 @@
 
 #include "ccmi.h"
 #include "device.h"
+#include "hip_check.h"
 #include "prof.h"
 
 namespace ccmi {
 
 hipError_t launchAcceptActions(const DevTables& T, const DevProgram& prog, const AcceptRow* rows, int64_t nRows,
                                int8_t* out, hipStream_t st);
-hipError_t launchAcceptMask(const DevTables& T, const DevProgram& prog, const MaskRow* rows, int64_t nSources,
+hipError_t launchAcceptMask(const DevTables& T, const DevProgram& prog, const SourceRow* rows, int64_t nSources,
                             unsigned long long* out, hipStream_t st);
-hipError_t launchAcceptSwaps(const DevTables& T, const DevProgram& prog, const SwapRow* rows, int64_t nSources,
+hipError_t launchAcceptSwaps(const DevTables& T, const DevProgram& prog, const SourceRow* rows, int64_t nSources,
                              const int32_t* cands, int64_t m, int8_t* out, hipStream_t st);
 hipError_t launchBrokerStatsRows(const BrokerRec* brokers, const BrokerStatic* meta, int B, ccmi_basic_stats* out, int D,
                                  const double* dUtil, const double* dCap, const int32_t* dBroker,
@@ -30,23 +32,36 @@ hipError_t launchBrokerStatsDisks(const DiskMember* members, int64_t E, const Re
                                   ccmi_disk_stats* diskOut, hipStream_t st);
 
 namespace {
-void hipCheck(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
-}
-// the session's device current for the call (HIP's current device is per host thread), the caller's afterwards
-struct CurrentDevice {
-  int prev = -1;
-  explicit CurrentDevice(int ordinal) {
-    hipCheck(hipGetDevice(&prev), "hipGetDevice");
-    if (prev != ordinal) hipCheck(hipSetDevice(ordinal), "hipSetDevice");
-    else prev = -1;
-  }
-  ~CurrentDevice() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 constexpr double kAcceptWaitSeconds = 120.0;
 }  // namespace
+
+// The session's device current and the device-scan phase open for the call; plain launches on the session stream, so the
+// server stops first (none is resident between API calls anyway).
+struct Device::PlainLaunch {
+  DeviceGuard dg;
+  PhaseScope ps;
+  Device& d;
+  explicit PlainLaunch(Device& dev) : dg(dev.ordinal_), ps(PH_DEV_SCAN), d(dev) { d.stopServer(); }
+  // a call with nothing to launch still takes the pending row updates to the tables
+  bool nothingToDo(bool empty) {
+    if (empty) d.flushPending();
+    return empty;
+  }
+};
+
+template <class Launch>
+void Device::timedLaunch(Launch launch) {
+  if (timing) (void)hipEventRecord((hipEvent_t)ev0_, (hipStream_t)st_);
+  launch();
+  if (timing) (void)hipEventRecord((hipEvent_t)ev1_, (hipStream_t)st_);
+}
+
+void Device::addKernelMs(double& total) {
+  if (!timing) return;
+  float ms = 0.f;
+  hipCheck(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_), "hipEventElapsedTime");
+  total += ms;
+}
 
 // the output buffer of one chunk, grown to the largest chunk so far
 void Device::ensureAccept(size_t bytes) {
@@ -58,133 +73,97 @@ void Device::ensureAccept(size_t bytes) {
   acceptCap_ = bytes;
 }
 
+template <class Fill, class Launch>
+void Device::acceptChunk(size_t req, Fill fill, size_t outBytes, Launch launch, void* dst, const char* kernel,
+                         const char* copy) {
+  const hipStream_t st = (hipStream_t)st_;
+  // the chunk's request goes into HBM with the pending row updates (prep; the first chunk carries them all)
+  const Staged g = packUpdates(req);
+  fill(hStage_ + g.end);
+  launchPrepFor(g, req, false);
+  ensureAccept(outBytes);
+  timedLaunch([&] { hipCheck(launch(st), kernel); });
+  hipCheck(hipMemcpyAsync(dst, dAccept_, outBytes, hipMemcpyDeviceToHost, st), copy);
+  streamWait(kernel, kAcceptWaitSeconds);
+  perf.syncs++;
+  perf.acceptLaunches++;  // acceptCells is the caller's count: it knows which rows are padding and which exits were early
+  addKernelMs(perf.acceptKernelMs);
+}
+
 void Device::acceptBatch(const DevProgram& prog, const AcceptRow* rows, int64_t nRows, int64_t nMoveRows, int8_t* out) {
-  CurrentDevice cur(ordinal_);
-  PhaseScope ps(PH_DEV_SCAN);
-  stopServer();  // a plain launch on the session stream (no server is resident between API calls anyway)
+  PlainLaunch call(*this);
   if (nRows % 64 != 0 || nMoveRows % 64 != 0 || nMoveRows < 0 || nMoveRows > nRows)
     throw std::logic_error("acceptBatch takes whole wavefronts of each row kind");
   if (prog.nGoals < 1 || prog.nGoals > kMaxGoals) throw std::logic_error("acceptBatch: goal count");
-  if (nRows == 0) {
-    flushPending();
-    return;
-  }
+  if (call.nothingToDo(nRows == 0)) return;
   const size_t G = (size_t)prog.nGoals;
   const int64_t chunk = acceptChunkRows_;  // a multiple of 64, so a chunk boundary never splits a wavefront
-  const hipStream_t st = (hipStream_t)st_;
   for (int64_t r0 = 0; r0 < nRows; r0 += chunk) {
     const int64_t n = std::min(chunk, nRows - r0);
-    // the chunk's rows go into HBM with the pending row updates (prep; the first chunk carries them all)
     const size_t req = (size_t)n * sizeof(AcceptRow);
-    const Staged g = packUpdates(req);
-    std::memcpy(hStage_ + g.end, rows + r0, req);
-    launchPrepFor(g, req, false);
-    ensureAccept((size_t)n * G);
-    if (timing) (void)hipEventRecord((hipEvent_t)ev0_, st);
-    hipCheck(launchAcceptActions(tables(), prog, (const AcceptRow*)dReq_, n, dAccept_, st), "accept_actions");
-    if (timing) (void)hipEventRecord((hipEvent_t)ev1_, st);
-    hipCheck(hipMemcpyAsync(out + (size_t)r0 * G, dAccept_, (size_t)n * G, hipMemcpyDeviceToHost, st), "D2H acceptance");
-    streamWait("accept_actions", kAcceptWaitSeconds);
-    perf.syncs++;
-    perf.acceptLaunches++;  // acceptCells is the caller's count: it knows which rows are padding
-    if (timing) {
-      float ms = 0.f;
-      hipCheck(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_), "hipEventElapsedTime");
-      perf.acceptKernelMs += ms;
-    }
+    acceptChunk(
+        req, [&](char* p) { std::memcpy(p, rows + r0, req); }, (size_t)n * G,
+        [&](hipStream_t st) { return launchAcceptActions(tables(), prog, (const AcceptRow*)dReq_, n, dAccept_, st); },
+        out + (size_t)r0 * G, "accept_actions", "D2H acceptance");
   }
 }
 
-void Device::maskBatch(const DevProgram& prog, const MaskRow* rows, int64_t nSources, uint64_t* out) {
-  CurrentDevice cur(ordinal_);
-  PhaseScope ps(PH_DEV_SCAN);
-  stopServer();  // a plain launch on the session stream, as acceptBatch
+void Device::maskBatch(const DevProgram& prog, const SourceRow* rows, int64_t nSources, uint64_t* out) {
+  PlainLaunch call(*this);
   if (nSources < 0 || prog.nGoals < 0 || prog.nGoals > kMaxGoals) throw std::logic_error("maskBatch: counts");
-  if (nSources == 0) {
-    flushPending();
-    return;
-  }
+  if (call.nothingToDo(nSources == 0)) return;
   const size_t W = (size_t)maskWords();
   const int64_t chunk = maskChunkSources_;
-  const hipStream_t st = (hipStream_t)st_;
   for (int64_t s0 = 0; s0 < nSources; s0 += chunk) {
     const int64_t n = std::min(chunk, nSources - s0);
-    // the chunk's sources go into HBM with the pending row updates (prep; the first chunk carries them all)
-    const size_t req = (size_t)n * sizeof(MaskRow);
-    const Staged g = packUpdates(req);
-    std::memcpy(hStage_ + g.end, rows + s0, req);
-    launchPrepFor(g, req, false);
-    const size_t bytes = (size_t)n * W * sizeof(uint64_t);
-    ensureAccept(bytes);
-    if (timing) (void)hipEventRecord((hipEvent_t)ev0_, st);
-    hipCheck(launchAcceptMask(tables(), prog, (const MaskRow*)dReq_, n, (unsigned long long*)dAccept_, st), "accept_mask");
-    if (timing) (void)hipEventRecord((hipEvent_t)ev1_, st);
-    hipCheck(hipMemcpyAsync(out + (size_t)s0 * W, dAccept_, bytes, hipMemcpyDeviceToHost, st), "D2H masks");
-    streamWait("accept_mask", kAcceptWaitSeconds);
-    perf.syncs++;
-    perf.acceptLaunches++;  // acceptCells is the caller's count
-    if (timing) {
-      float ms = 0.f;
-      hipCheck(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_), "hipEventElapsedTime");
-      perf.acceptKernelMs += ms;
-    }
+    const size_t req = (size_t)n * sizeof(SourceRow);
+    acceptChunk(
+        req, [&](char* p) { std::memcpy(p, rows + s0, req); }, (size_t)n * W * sizeof(uint64_t),
+        [&](hipStream_t st) {
+          return launchAcceptMask(tables(), prog, (const SourceRow*)dReq_, n, (unsigned long long*)dAccept_, st);
+        },
+        out + (size_t)s0 * W, "accept_mask", "D2H masks");
   }
 }
 
-void Device::swapGridBatch(const DevProgram& prog, const SwapRow* rows, int64_t nSources, const int32_t* cands, int64_t m,
-                           int8_t* out) {
-  CurrentDevice cur(ordinal_);
-  PhaseScope ps(PH_DEV_SCAN);
-  stopServer();  // a plain launch on the session stream, as acceptBatch
+void Device::swapGridBatch(const DevProgram& prog, const SourceRow* rows, int64_t nSources, const int32_t* cands,
+                           int64_t m, int8_t* out) {
+  PlainLaunch call(*this);
   if (nSources < 0 || m < 0 || prog.nGoals < 0 || prog.nGoals > kMaxGoals) throw std::logic_error("swapGridBatch: counts");
   if (m > kMaxSwapCandidates)
     throw std::invalid_argument("a swap grid takes at most " + std::to_string(kMaxSwapCandidates) + " candidates");
-  if (nSources == 0 || m == 0) {
-    flushPending();
-    return;
-  }
+  if (call.nothingToDo(nSources == 0 || m == 0)) return;
   // a row of the device buffer is whole wavefronts: a wave's 64 codes are one aligned 64-byte run
   const size_t pitch = (size_t)((m + 63) / 64 * 64);
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(65535, swapChunkCells_ / (int64_t)pitch));
-  const size_t oCand = (size_t)std::min(chunk, nSources) * sizeof(SwapRow);  // 16-byte rows: the ids stay aligned
-  const hipStream_t st = (hipStream_t)st_;
+  const size_t oCand = (size_t)std::min(chunk, nSources) * sizeof(SourceRow);  // 16-byte rows: the ids stay aligned
+  const bool compact = pitch != (size_t)m;
   for (int64_t s0 = 0; s0 < nSources; s0 += chunk) {
     const int64_t n = std::min(chunk, nSources - s0);
-    // the chunk's sources and the candidate ids go into HBM with the pending row updates (prep; the first chunk
-    // carries them all)
-    const size_t req = oCand + (size_t)m * sizeof(int32_t);
-    const Staged g = packUpdates(req);
-    std::memcpy(hStage_ + g.end, rows + s0, (size_t)n * sizeof(SwapRow));
-    std::memcpy(hStage_ + g.end + oCand, cands, (size_t)m * sizeof(int32_t));
-    launchPrepFor(g, req, false);
-    ensureAccept((size_t)n * pitch);
-    if (timing) (void)hipEventRecord((hipEvent_t)ev0_, st);
-    hipCheck(launchAcceptSwaps(tables(), prog, (const SwapRow*)dReq_, n, (const int32_t*)(dReq_ + oCand), m, dAccept_, st),
-             "accept_swaps");
-    if (timing) (void)hipEventRecord((hipEvent_t)ev1_, st);
     // back without the pitch: one contiguous copy of the chunk, then a host compaction of its rows (a 2-D copy of the
     // same 64 x 825 codes took 0.6 ms against 0.08 ms for the whole call this way)
     int8_t* dst = out + (size_t)s0 * (size_t)m;
-    const bool compact = pitch != (size_t)m;
     if (compact) swapHost_.resize((size_t)n * pitch);
-    hipCheck(hipMemcpyAsync(compact ? swapHost_.data() : dst, dAccept_, (size_t)n * pitch, hipMemcpyDeviceToHost, st),
-             "D2H swap codes");
-    streamWait("accept_swaps", kAcceptWaitSeconds);
+    acceptChunk(
+        oCand + (size_t)m * sizeof(int32_t),  // the chunk's sources, then the candidate ids
+        [&](char* p) {
+          std::memcpy(p, rows + s0, (size_t)n * sizeof(SourceRow));
+          std::memcpy(p + oCand, cands, (size_t)m * sizeof(int32_t));
+        },
+        (size_t)n * pitch,
+        [&](hipStream_t st) {
+          return launchAcceptSwaps(tables(), prog, (const SourceRow*)dReq_, n, (const int32_t*)(dReq_ + oCand), m, dAccept_,
+                                   st);
+        },
+        compact ? swapHost_.data() : dst, "accept_swaps", "D2H swap codes");
     if (compact)
       for (int64_t i = 0; i < n; ++i) std::memcpy(dst + (size_t)i * (size_t)m, swapHost_.data() + (size_t)i * pitch, (size_t)m);
-    perf.syncs++;
-    perf.acceptLaunches++;  // acceptCells is the caller's count
-    if (timing) {
-      float ms = 0.f;
-      hipCheck(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_), "hipEventElapsedTime");
-      perf.acceptKernelMs += ms;
-    }
   }
 }
 
 void Device::uploadStatsStatic(const BrokerStatic* meta, int H, const int32_t* hOff, const int32_t* hBrk,
                                const int32_t* hIdx, const int32_t* dBroker) {
-  CurrentDevice cur(ordinal_);
+  DeviceGuard cur(ordinal_);
   stopServer();
   if (dStatMeta_) throw std::logic_error("uploadStatsStatic: once per session");
   if (H < 1 || H > B_) throw std::logic_error("uploadStatsStatic: host count");
@@ -207,9 +186,7 @@ void Device::uploadStatsStatic(const BrokerStatic* meta, int H, const int32_t* h
 
 void Device::brokerStats(ccmi_basic_stats* brokers, ccmi_basic_stats* hosts, ccmi_disk_stats* disks,
                          const DiskMember* members, int64_t nMembers, uint64_t memberVer) {
-  CurrentDevice cur(ordinal_);
-  PhaseScope ps(PH_DEV_SCAN);
-  stopServer();  // plain launches on the session stream, as maskBatch
+  PlainLaunch call(*this);
   if (!dStatMeta_) throw std::logic_error("brokerStats before uploadStatsStatic");
   if (!brokers || nMembers < 0) throw std::logic_error("brokerStats: arguments");
   const bool withDisks = disks && D_ > 0;
@@ -234,21 +211,21 @@ void Device::brokerStats(ccmi_basic_stats* brokers, ccmi_basic_stats* hosts, ccm
     statMemberVer_ = memberVer;
   }
   ccmi_basic_stats* dHosts = dStatRows_ + B_;
-  if (timing) (void)hipEventRecord((hipEvent_t)ev0_, st);
-  hipCheck(launchBrokerStatsRows(brokers_, dStatMeta_, B_, dStatRows_, withDisks ? D_ : 0, dDUtilIn_, dDCap_, dStatDBroker_,
-                                 dStatDisks_, st),
-           "broker_stats_rows");
   int launches = 1;
-  if (hosts) {
-    hipCheck(launchBrokerStatsHosts(dStatRows_, dStatHOff_, dStatHBrk_, dStatHIdx_, statH_, B_, dHosts, st),
-             "broker_stats_hosts");
-    launches++;
-  }
-  if (withDisks && statMembers_ > 0) {
-    hipCheck(launchBrokerStatsDisks(dStatMembers_, statMembers_, replicas_, R_, D_, dStatDisks_, st), "broker_stats_disks");
-    launches++;
-  }
-  if (timing) (void)hipEventRecord((hipEvent_t)ev1_, st);
+  timedLaunch([&] {
+    hipCheck(launchBrokerStatsRows(brokers_, dStatMeta_, B_, dStatRows_, withDisks ? D_ : 0, dDUtilIn_, dDCap_,
+                                   dStatDBroker_, dStatDisks_, st),
+             "broker_stats_rows");
+    if (hosts) {
+      hipCheck(launchBrokerStatsHosts(dStatRows_, dStatHOff_, dStatHBrk_, dStatHIdx_, statH_, B_, dHosts, st),
+               "broker_stats_hosts");
+      launches++;
+    }
+    if (withDisks && statMembers_ > 0) {
+      hipCheck(launchBrokerStatsDisks(dStatMembers_, statMembers_, replicas_, R_, D_, dStatDisks_, st), "broker_stats_disks");
+      launches++;
+    }
+  });
   hipCheck(hipMemcpyAsync(brokers, dStatRows_, (size_t)B_ * sizeof(ccmi_basic_stats), hipMemcpyDeviceToHost, st),
            "D2H broker stats");
   if (hosts)
@@ -265,11 +242,7 @@ void Device::brokerStats(ccmi_basic_stats* brokers, ccmi_basic_stats* hosts, ccm
   perf.statsBytes += (int64_t)B_ * (int64_t)(sizeof(BrokerRec) + sizeof(BrokerStatic) + sizeof(ccmi_basic_stats)) +
                      (hosts ? (int64_t)B_ * (int64_t)sizeof(ccmi_basic_stats) + (int64_t)statH_ * 136 : 0) +
                      (withDisks ? (int64_t)D_ * (16 + 4 + (int64_t)sizeof(ccmi_disk_stats)) + statMembers_ * 12 : 0);
-  if (timing) {
-    float ms = 0.f;
-    hipCheck(hipEventElapsedTime(&ms, (hipEvent_t)ev0_, (hipEvent_t)ev1_), "hipEventElapsedTime");
-    perf.statsKernelMs += ms;
-  }
+  addKernelMs(perf.statsKernelMs);
 }
 
 }  // namespace ccmi

@@ -232,19 +232,14 @@ struct alignas(16) AcceptRow {
 };
 static_assert(sizeof(AcceptRow) == 16, "AcceptRow is one 16-byte load");
 
-// One source of a destination-mask batch (kernels/accept_mask.hip) as the host resolved it: the replica of partition p
-// on broker src that moves or gives up leadership, and the DevAction (DA_MOVE or DA_LEADERSHIP).
-struct alignas(16) MaskRow {
+// One source of a destination-mask batch (kernels/accept_mask.hip) or of a swap grid (kernels/accept_swap.hip) as the
+// host resolved it: the replica of partition p on broker src, and the DevAction: DA_MOVE or DA_LEADERSHIP for a mask
+// source (the replica moves or gives up leadership), DA_SWAP for a grid source (the candidates of the grid are plain
+// replica ids).
+struct alignas(16) SourceRow {
   int32_t sr, p, src, action;
 };
-static_assert(sizeof(MaskRow) == 16, "MaskRow is one 16-byte load");
-
-// One source of a swap grid (kernels/accept_swap.hip) as the host resolved it: the replica of partition p on broker src;
-// action is DA_SWAP. The candidates of the grid are plain replica ids.
-struct alignas(16) SwapRow {
-  int32_t sr, p, src, action;
-};
-static_assert(sizeof(SwapRow) == 16, "SwapRow is one 16-byte load");
+static_assert(sizeof(SourceRow) == 16, "SourceRow is one 16-byte load");
 constexpr int64_t kMaxSwapCandidates = INT32_MAX - 63;  // candidates of one grid: the padded row still indexes as int32
 
 // ccmi_broker_stats (kernels/broker_stats.hip): what a broker's row takes from outside its BrokerRec (static: the

@@ -5,7 +5,7 @@
 //                   loop of AbstractGoal.maybeApplyBalancingAction (AbstractGoal.java:243-270) asks of each candidate
 //                   broker, for all brokers at once, one bit per broker.
 // One wavefront (a workgroup) produces one output word: 64 consecutive destination brokers of one source. The source
-// index is blockIdx.x (the dimension that can be large) and the word index blockIdx.y, so the MaskRow, the source's
+// index is blockIdx.x (the dimension that can be large) and the word index blockIdx.y, so the SourceRow, the source's
 // replica, partition and broker records and everything derived from them are wave-uniform: scalar loads, scalar
 // registers. A lane loads only its destination's BrokerRec (64 consecutive 128-byte records per wave), plus the topic
 // count cells the topic goals ask for. The goal loop is outermost with a scalar trip count; a wave leaves it once its
@@ -29,12 +29,12 @@ constexpr int kMaskWave = 64;
 
 // rows[0, nSources); grid (nSources, W), W = (T.B + 63) / 64 words per source; out[source * W + word].
 __global__ __launch_bounds__(kMaskWave) void accept_mask(DevTables T, DevProgram prog,
-                                                         const MaskRow* __restrict__ rows,
+                                                         const SourceRow* __restrict__ rows,
                                                          unsigned long long* __restrict__ out) {
   const size_t source = blockIdx.x;
   const int word = blockIdx.y;
   const int lane = threadIdx.x;
-  const MaskRow a = rows[source];
+  const SourceRow a = rows[source];
   const int b = word * kMaskWave + lane;
   const bool inRange = b < T.B;
   const int dst = inRange ? b : T.B - 1;
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(kMaskWave) void accept_mask(DevTables T, DevProgram
   if (lane == 0) out[source * gridDim.y + word] = accepted;
 }
 
-hipError_t launchAcceptMask(const DevTables& T, const DevProgram& prog, const MaskRow* rows, int64_t nSources,
+hipError_t launchAcceptMask(const DevTables& T, const DevProgram& prog, const SourceRow* rows, int64_t nSources,
                             unsigned long long* out, hipStream_t st) {
   const int64_t W = ((int64_t)T.B + kMaskWave - 1) / kMaskWave;
   if (nSources <= 0 || nSources > INT32_MAX || T.B < 1 || W > 65535 || prog.nGoals < 0 || prog.nGoals > kMaxGoals)

@@ -6,7 +6,7 @@
 //                    broker) fails (:313), else the first verdict of the program's goals that is not ACCEPT
 //                    (AnalyzerUtils.java:169-179: 1 REPLICA_REJECT, 2 BROKER_REJECT), else 0.
 // One wavefront (a workgroup) produces 64 consecutive candidates of one source. The candidate block is blockIdx.x (the
-// dimension that can be large) and the source blockIdx.y, so the SwapRow, the source's replica, partition and broker
+// dimension that can be large) and the source blockIdx.y, so the SourceRow, the source's replica, partition and broker
 // records and everything derived from them are wave-uniform: scalar loads, scalar registers. A lane loads its
 // candidate's replica id, then its ReplicaRec, then that replica's PartitionRec and BrokerRec (three dependent levels),
 // plus the topic cells the topic goals ask for. The goal loop is outermost with a scalar trip count; every lane
@@ -31,12 +31,12 @@ constexpr int kSwapWave = 64;
 
 // rows[0, gridDim.y), cands[0, m); grid (pitch / 64, nSources); out[source * pitch + candidate].
 __global__ __launch_bounds__(kSwapWave) void accept_swaps(DevTables T, DevProgram prog,
-                                                          const SwapRow* __restrict__ rows,
+                                                          const SourceRow* __restrict__ rows,
                                                           const int32_t* __restrict__ cands, int m, int64_t pitch,
                                                           int8_t* __restrict__ out) {
   const size_t source = blockIdx.y;
   const int lane = threadIdx.x;
-  const SwapRow a = rows[source];
+  const SourceRow a = rows[source];
   const int64_t j = (int64_t)blockIdx.x * kSwapWave + lane;
   const bool inRange = j < m;
   const int dr = cands[inRange ? j : (int64_t)m - 1];
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(kSwapWave) void accept_swaps(DevTables T, DevProgra
   if (inRange) out[source * (size_t)pitch + (size_t)j] = (int8_t)code;
 }
 
-hipError_t launchAcceptSwaps(const DevTables& T, const DevProgram& prog, const SwapRow* rows, int64_t nSources,
+hipError_t launchAcceptSwaps(const DevTables& T, const DevProgram& prog, const SourceRow* rows, int64_t nSources,
                              const int32_t* cands, int64_t m, int8_t* out, hipStream_t st) {
   const int64_t blocks = (m + kSwapWave - 1) / kSwapWave;
   if (nSources <= 0 || nSources > 65535 || m <= 0 || m > kMaxSwapCandidates || prog.nGoals < 0 || prog.nGoals > kMaxGoals)

@@ -4,25 +4,17 @@ device call (kernels/accept.hip), against the oracle cell by cell and against th
 The reference is OracleCluster.action_acceptance_by_goal on an oracle cluster that ran the same chain (and, for the
 state-tracking test, applied the same external actions). Every comparison is exact: the verdicts are small integers.
 """
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import ccmi
-from oracle_binding import OracleCluster
+from acceptance_support import (ACCEPT, BROKER_REJECT, CAPACITY_GOALS, CAPACITY_MIXED, CAPACITY_THRESHOLDS, DEFAULT_GOALS,
+                                LEADERSHIP, MOVE, REPLICA_REJECT, SEED, SWAP, ChainCase, Placement,
+                                directed_capacity_actions, props, run_in_fresh_process, status_of)
 from parity import constraint
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEFAULT_GOALS = list(ccmi.DEFAULT_GOALS)
-PROPS = dict(num_racks=5, num_brokers=20, num_replicas=6000, num_topics=300)
-SEED = 20261019
+PROPS = props(20)
 PER_TYPE = 700
-MOVE, LEADERSHIP, SWAP = 0, 1, 2
-ACCEPT, REPLICA_REJECT, BROKER_REJECT = 0, 1, 2
 # goals that both accept and reject some action of the random sample (checked on the oracle's matrix)
 MIXED_GOALS = ["RackAwareGoal", "ReplicaDistributionGoal", "DiskUsageDistributionGoal",
                "NetworkInboundUsageDistributionGoal", "NetworkOutboundUsageDistributionGoal", "CpuUsageDistributionGoal",
@@ -34,20 +26,6 @@ VERDICTS_BY_TYPE = {MOVE: {ACCEPT, REPLICA_REJECT, BROKER_REJECT}, LEADERSHIP: {
 
 
 # ------------------------------------------------------------------------------------------------ samples
-class Placement:
-    """Partition membership of a model (replica_distribution / leader_distribution order)."""
-
-    def __init__(self, desc, dist, leaders):
-        self.B = desc.num_brokers
-        self.off = list(desc.partition_offset[:desc.num_partitions + 1])
-        self.dist = list(dist)
-        self.leaders = list(leaders)
-        self.slot_part = np.repeat(np.arange(len(self.off) - 1), np.diff(self.off))
-
-    def brokers(self, p):
-        return self.dist[self.off[p]:self.off[p + 1]]
-
-
 def random_actions(pl, rs, per_type):
     """per_type replica moves (a random replica to a broker not hosting the partition), leadership moves (the leader to a
     random follower) and swaps (two replicas of different partitions on different brokers, neither broker hosting the
@@ -92,19 +70,14 @@ def single_calls(cm, goals, actions):
     return out
 
 
-class Case:
+class Case(ChainCase):
     """A product session and an oracle cluster after the same chain, a random sample and the oracle's matrix of it."""
 
     def __init__(self, lib, max_replicas):
-        self.bc = constraint(1.05, max_replicas=max_replicas)
-        self.buf = ccmi.RandomCluster.generate(lib, **PROPS)
-        self.cm = ccmi.ClusterModel.from_buffers(self.buf)
-        self.oc = OracleCluster.from_desc(self.buf.desc)
-        ccmi.GoalOptimizer(self.bc).optimizations(self.cm, ccmi.goals_from_names(DEFAULT_GOALS))
-        self.oc.optimize(DEFAULT_GOALS, self.bc)
-        assert self.cm.actions() == self.oc.actions()
-        pl = Placement(self.buf.desc, self.oc.replica_distribution(), self.oc.leader_distribution())
-        self.sample = random_actions(pl, np.random.RandomState(SEED), PER_TYPE)
+        buf = ccmi.RandomCluster.generate(lib, **PROPS)
+        super().__init__(lib, buf.desc, buf)
+        self.optimize(DEFAULT_GOALS, constraint(1.05, max_replicas=max_replicas))
+        self.sample = random_actions(self.placement(), np.random.RandomState(SEED), PER_TYPE)
         self.expected = oracle_matrix(self.oc, DEFAULT_GOALS, self.sample)
         self.expected.setflags(write=False)
 
@@ -203,87 +176,26 @@ def test_gpu_more_goal_columns_than_one_program(cases):
 
 
 # ------------------------------------------------------------------------------------------------ 3. chunk boundary
-_CHUNK_SCRIPT = r"""
-import json, sys
-import numpy as np
-sys.path.insert(0, {pkg!r}); sys.path.insert(0, {tests!r})
-import ccmi
-from parity import constraint
-lib = ccmi.Library.get({lib!r})
-buf = ccmi.RandomCluster.generate(lib, **{props!r})
-cm = ccmi.ClusterModel.from_buffers(buf)
-goals = list(ccmi.DEFAULT_GOALS)
-ccmi.GoalOptimizer(constraint(1.05, max_replicas=3000)).optimizations(cm, ccmi.goals_from_names(goals))
-acts = [tuple(a) for a in json.load(open({sample!r}))]
-cm.reset_perf()
-got = cm.actions_acceptance(goals, acts)
-json.dump(dict(matrix=got.tolist(), launches=cm.perf().accept_launches), open({out!r}, "w"))
-"""
-
-
 @pytest.mark.gpu
 def test_gpu_chunk_boundary_matches_oracle(cases, gpu_lib, tmp_path):
     """CCMI_ACCEPT_CHUNK_ROWS is read at session create: a fresh process with 96 (rounded down to one wavefront, 64
     rows) answers n = 257 in several launches — 172 moves and leadership moves in 192 rows, 85 swaps in 128."""
     c = cases(3000)
-    sample, out = tmp_path / "sample.json", tmp_path / "out.json"
-    json.dump(c.sample[:257], open(sample, "w"))
-    code = _CHUNK_SCRIPT.format(pkg=os.path.join(REPO, "cruise-control_amd"), tests=os.path.join(REPO, "tests"),
-                                lib=gpu_lib.path, props=PROPS, sample=str(sample), out=str(out))
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, CCMI_ACCEPT_CHUNK_ROWS="96"),
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    res = json.load(open(out))
-    assert res["launches"] == 5  # 320 rows in chunks of 64
-    assert (np.array(res["matrix"], dtype=np.int8) == c.expected[:257]).all()
+    matrix, launches = run_in_fresh_process(gpu_lib, tmp_path, PROPS, dict(CCMI_ACCEPT_CHUNK_ROWS="96"), c.sample[:257],
+                                            "cm.actions_acceptance(goals, [tuple(a) for a in sample])")
+    assert launches == 5  # 320 rows in chunks of 64
+    assert (np.array(matrix, dtype=np.int8) == c.expected[:257]).all()
 
 
 # ------------------------------------------------------------------------------------------------ 4. capacity goals
-CAPACITY_GOALS = ["ReplicaCapacityGoal", "DiskCapacityGoal", "NetworkInboundCapacityGoal",
-                  "NetworkOutboundCapacityGoal", "CpuCapacityGoal", "PotentialNwOutGoal"]
-# One threshold for all four resources makes only DiskCapacityGoal reject (the cluster's CPU, NW_IN and NW_OUT sit far
-# below any DISK threshold the chain survives), so each resource gets its own: 1.1 x its mean broker utilization
-# (CPU 0.0312, NW_IN 0.1142, NW_OUT 0.0515, DISK 0.1100 of capacity). The chain survives them (74 actions) and leaves the
-# most utilized brokers within one heavy replica of their limits.
-CAPACITY_THRESHOLDS = (0.0343, 0.1256, 0.0566, 0.1210)
-# the goals that both accept and reject some action of the directed sample (checked on the oracle): all five.
-# ReplicaCapacityGoal's rejects are the max_replicas=302 case of the matrix test.
-CAPACITY_MIXED = ["DiskCapacityGoal", "NetworkInboundCapacityGoal", "NetworkOutboundCapacityGoal", "CpuCapacityGoal",
-                  "PotentialNwOutGoal"]
-
-
-def directed_capacity_actions(desc, pl, oc, k=6):
-    """For each resource, the replicas of the k partitions that carry most of it x the k most utilized brokers of it
-    that do not host the partition (replica moves), and those partitions' leaders to their followers."""
-    W, R, P = desc.num_windows, desc.num_replicas, desc.num_partitions
-    load = np.array(desc.replica_load[:R * 6 * W], dtype=np.float64).reshape(R, 6, W).mean(axis=2)
-    part = np.array(desc.replica_partition[:R])
-    acts = []
-    # resource -> the ccmi_metric that carries it on a leader: CPU, NW_IN (leader bytes in), NW_OUT, DISK
-    for res, metric in ((0, 0), (1, 2), (2, 3), (3, 1)):
-        weight = np.zeros(P)
-        np.maximum.at(weight, part, load[:, metric])
-        util = [oc.broker_util(b, res) for b in range(pl.B)]
-        hot = sorted(range(pl.B), key=lambda b: -util[b])[:k]
-        for p in (int(x) for x in np.argsort(-weight, kind="stable")[:k]):
-            for src in pl.brokers(p):
-                acts += [(MOVE, p, src, dst, -1, -1, -1) for dst in hot if dst not in pl.brokers(p)]
-            acts += [(LEADERSHIP, p, pl.leaders[p], dst, -1, -1, -1) for dst in pl.brokers(p) if dst != pl.leaders[p]]
-    return acts
-
-
 @pytest.mark.gpu
 def test_gpu_capacity_goals_directed_sample(gpu_lib, oracle_lib):
     bc = constraint(1.05, max_replicas=3000)
     bc.capacity_threshold = CAPACITY_THRESHOLDS
-    buf = ccmi.RandomCluster.generate(gpu_lib, **PROPS)
-    cm = ccmi.ClusterModel.from_buffers(buf)
-    oc = OracleCluster.from_desc(buf.desc)
-    ccmi.GoalOptimizer(bc).optimizations(cm, ccmi.goals_from_names(CAPACITY_GOALS))
-    oc.optimize(CAPACITY_GOALS, bc)
-    assert cm.actions() == oc.actions()
-    pl = Placement(buf.desc, oc.replica_distribution(), oc.leader_distribution())
-    acts = directed_capacity_actions(buf.desc, pl, oc)
+    c = ChainCase.random(gpu_lib, **PROPS)
+    c.optimize(CAPACITY_GOALS, bc)
+    cm, oc = c.cm, c.oc
+    acts = directed_capacity_actions(c.desc, c.placement(), oc)
     expected = oracle_matrix(oc, CAPACITY_GOALS, acts)
     for name in CAPACITY_MIXED:
         col = expected[:, CAPACITY_GOALS.index(name)]
@@ -296,14 +208,6 @@ def test_gpu_capacity_goals_directed_sample(gpu_lib, oracle_lib):
 
 
 # ------------------------------------------------------------------------------------------------ 5. errors
-def _status_of(call):
-    try:
-        call()
-    except ccmi.CruiseControlError as e:
-        return type(e), getattr(e, "first_invalid", None)
-    return None, None
-
-
 @pytest.mark.gpu
 def test_gpu_errors_are_the_single_calls(cases):
     c = cases(3000)
@@ -311,35 +215,34 @@ def test_gpu_errors_are_the_single_calls(cases):
     # a kind the session has not optimized
     with pytest.raises(ccmi.IllegalArgumentException):
         cm.action_acceptance_by_goal("RackAwareDistributionGoal", *acts[0])
-    assert _status_of(lambda: cm.actions_acceptance(["RackAwareGoal", "RackAwareDistributionGoal"], acts)) == \
+    assert status_of(lambda: cm.actions_acceptance(["RackAwareGoal", "RackAwareDistributionGoal"], acts)) == \
         (ccmi.IllegalArgumentException, -1)
     # the source broker does not host the partition, at index 5 of 9
     p = acts[5][1]
-    stranger = next(b for b in range(20) if b not in Placement(c.buf.desc, c.oc.replica_distribution(),
-                                                               c.oc.leader_distribution()).brokers(p))
+    stranger = next(b for b in range(20) if b not in c.placement().brokers(p))
     bad = (MOVE, p, stranger, acts[5][2], -1, -1, -1)
     with pytest.raises(ccmi.IllegalArgumentException):
         cm.action_acceptance_by_goal("RackAwareGoal", *bad)
-    assert _status_of(lambda: cm.actions_acceptance(DEFAULT_GOALS, acts[:5] + [bad] + acts[6:])) == \
+    assert status_of(lambda: cm.actions_acceptance(DEFAULT_GOALS, acts[:5] + [bad] + acts[6:])) == \
         (ccmi.IllegalArgumentException, 5)
     # a swap whose destination broker does not host the destination partition
     swap = next(a for a in c.sample if a[0] == SWAP)
     bad_swap = (SWAP, swap[1], swap[2], swap[3], swap[1], -1, -1)
     with pytest.raises(ccmi.IllegalArgumentException):
         cm.action_acceptance_by_goal("RackAwareGoal", *bad_swap)
-    assert _status_of(lambda: cm.actions_acceptance(DEFAULT_GOALS, [acts[0], bad_swap])) == \
+    assert status_of(lambda: cm.actions_acceptance(DEFAULT_GOALS, [acts[0], bad_swap])) == \
         (ccmi.IllegalArgumentException, 1)
     # an unknown action type, and an intra-broker type asked of inter-broker goals
     for typ in (7, 3):
         unknown = (typ,) + tuple(acts[2][1:])
         with pytest.raises(ccmi.IllegalArgumentException):
             cm.action_acceptance_by_goal("RackAwareGoal", *unknown)
-        assert _status_of(lambda: cm.actions_acceptance(DEFAULT_GOALS, acts[:2] + [unknown])) == \
+        assert status_of(lambda: cm.actions_acceptance(DEFAULT_GOALS, acts[:2] + [unknown])) == \
             (ccmi.IllegalArgumentException, 2)
     # indices outside the model are refused before the device sees them
-    assert _status_of(lambda: cm.actions_acceptance(DEFAULT_GOALS, [(MOVE, 10 ** 6, 0, 1, -1, -1, -1)])) == \
+    assert status_of(lambda: cm.actions_acceptance(DEFAULT_GOALS, [(MOVE, 10 ** 6, 0, 1, -1, -1, -1)])) == \
         (ccmi.IllegalArgumentException, 0)
-    assert _status_of(lambda: cm.actions_acceptance(DEFAULT_GOALS, [(MOVE, acts[0][1], acts[0][2], 20, -1, -1, -1)])) == \
+    assert status_of(lambda: cm.actions_acceptance(DEFAULT_GOALS, [(MOVE, acts[0][1], acts[0][2], 20, -1, -1, -1)])) == \
         (ccmi.IllegalArgumentException, 0)
     # the session still answers afterwards
     assert (cm.actions_acceptance(DEFAULT_GOALS, acts) == c.expected[:9]).all()
@@ -381,7 +284,7 @@ def test_gpu_batch_after_session_apply_matches_oracle(gpu_lib, oracle_lib):
     assert {a[0] for a in external} == {MOVE, LEADERSHIP, SWAP}
     assert c.cm.apply(external) == len(external)
     c.oc.apply(external)
-    pl = Placement(c.buf.desc, c.oc.replica_distribution(), c.oc.leader_distribution())
+    pl = c.placement()
     again = random_actions(pl, np.random.RandomState(SEED + 1), 100)
     # actions on the moved partitions and brokers themselves: the reverse of every external action
     again += [(a[0], a[1], a[3], a[2], a[4], -1, -1) for a in external if a[0] != SWAP]
@@ -400,13 +303,9 @@ def test_gpu_shared_hosts_match_oracle(gpu_lib, oracle_lib):
     from test_hosts import HOST_GOALS, SHARED, _model
 
     flat = _model(SHARED)
-    cm = ccmi.ClusterModel(flat.desc, device=0, lib=gpu_lib, keepalive=flat)
-    oc = OracleCluster.from_desc(flat.desc)
-    bc = ccmi.BalancingConstraint()
-    ccmi.GoalOptimizer(bc).optimizations(cm, ccmi.goals_from_names(HOST_GOALS))
-    oc.optimize(HOST_GOALS, bc)
-    assert cm.actions() == oc.actions()
-    pl = Placement(flat.desc, oc.replica_distribution(), oc.leader_distribution())
+    c = ChainCase(gpu_lib, flat.desc, flat)
+    c.optimize(HOST_GOALS, ccmi.BalancingConstraint())
+    cm, oc, pl = c.cm, c.oc, c.placement()
     P = flat.desc.num_partitions
     acts = []
     for p in range(P):

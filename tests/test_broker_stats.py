@@ -22,19 +22,16 @@ import numpy as np
 import pytest
 
 import ccmi
-from oracle_binding import OracleCluster
+from acceptance_support import DEFAULT_GOALS, LEADERSHIP, MOVE, SWAP, ChainCase, props
 from parity import assign_shared_hosts, constraint
 from test_hosts import SHARED, _model as hosts_model
 from test_ingest import _random_cluster_via_builder
 from test_jbod import INTRA, rebalance_constraint
-from test_moves_acceptance_mask import props
 
 pytestmark = pytest.mark.gpu
 
-DEFAULT_GOALS = list(ccmi.DEFAULT_GOALS)
 CPU, NW_IN, NW_OUT, DISK = 0, 1, 2, 3
 M_LBI, M_LBO, M_RBI, M_RBO = 2, 3, 4, 5
-MOVE, LEADERSHIP, SWAP = 0, 1, 2
 DEAD = ccmi.BROKER_STATES["DEAD"]
 EXACT = ("disk_mb", "disk_pct", "cpu_pct", "nw_out_rate", "disk_capacity_mb", "network_in_capacity",
          "network_out_capacity", "num_core", "replicas", "leaders", "broker", "state", "host", "rack")
@@ -191,27 +188,12 @@ CHAIN_COLUMNS = ["disk_mb", "disk_pct", "cpu_pct", "nw_out_rate", "replicas", "l
                  "pnw_out_rate", "follower_nw_in_rate"]
 
 
-class Case:
-    """A product session and an oracle cluster over one desc; optimize() runs the same chain on both."""
-
-    def __init__(self, lib, desc, keepalive):
-        self.desc, self.keep = desc, keepalive
-        self.cm = ccmi.ClusterModel(desc, lib=lib, keepalive=keepalive)
-        self.oc = OracleCluster.from_desc(desc)
-
-    def optimize(self, goals, bc, **kwargs):
-        res = ccmi.GoalOptimizer(bc).optimizations(self.cm, ccmi.goals_from_names(goals), **kwargs)
-        self.oc.optimize(goals, bc)
-        assert self.cm.actions() == self.oc.actions()
-        return res
-
+class Case(ChainCase):
     def expected(self):
         return Expected(self.desc, self.oc, self.oc.actions())
 
 
-def random_case(lib, **cluster_props):
-    buf = ccmi.RandomCluster.generate(lib, **cluster_props)
-    return Case(lib, buf.desc, buf)
+random_case = Case.random
 
 
 # ------------------------------------------------------------------------------------------------ T1

@@ -5,24 +5,15 @@ The reference of every bit is the oracle: one OracleCluster.action_acceptance_by
 cluster that ran the same chain (the action logs are asserted equal first). Legitimacy (GoalUtils.legitMove) is
 computed in numpy from the oracle's replica_distribution / leader_distribution and the desc. Every comparison is exact.
 """
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import ccmi
-from oracle_binding import OracleCluster
+from acceptance_support import (CAPACITY_GOALS, CAPACITY_MIXED, CAPACITY_THRESHOLDS, DEFAULT_GOALS, LEADERSHIP, MOVE,
+                                SEED, SWAP, ChainCase, directed_capacity_actions, props, run_in_fresh_process, status_of)
 from parity import constraint
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEFAULT_GOALS = list(ccmi.DEFAULT_GOALS)
-SEED = 20261019
 PER_TYPE = 150
-MOVE, LEADERSHIP, SWAP = 0, 1, 2
-BAD_DISKS = ccmi.BROKER_STATES["BAD_DISKS"]
 # goals that both set and clear legit bits of the sample at 130 brokers (checked on the oracle's data)
 MIXED_FOR_MOVES = ["RackAwareGoal", "ReplicaDistributionGoal", "DiskUsageDistributionGoal",
                    "NetworkInboundUsageDistributionGoal", "NetworkOutboundUsageDistributionGoal",
@@ -32,41 +23,17 @@ MIXED_FOR_LEADERSHIP = ["NetworkOutboundUsageDistributionGoal", "CpuUsageDistrib
                         "LeaderReplicaDistributionGoal", "LeaderBytesInDistributionGoal"]
 
 
-def props(num_brokers, **more):
-    return dict(num_racks=5, num_brokers=num_brokers, num_replicas=6000, num_topics=300, **more)
-
-
 # ------------------------------------------------------------------------------------------------ the reference
-class Placement:
-    """Partition membership of a model (replica_distribution / leader_distribution order) as a [P, B] matrix."""
-
-    def __init__(self, desc, dist, leaders):
-        self.B, self.P = desc.num_brokers, desc.num_partitions
-        self.off = list(desc.partition_offset[:self.P + 1])
-        self.dist = list(dist)
-        self.leaders = list(leaders)
-        slot_part = np.repeat(np.arange(self.P), np.diff(self.off))
-        self.hosts = np.zeros((self.P, self.B), dtype=bool)
-        self.hosts[slot_part, self.dist] = True
-        # Partition._ineligibleBrokers: the BAD_DISKS brokers that held an offline replica of the partition (the desc)
-        self.ineligible = np.zeros((self.P, self.B), dtype=bool)
-        for r in range(desc.num_replicas):
-            if desc.replica_offline[r] and desc.broker_state[desc.replica_broker[r]] == BAD_DISKS:
-                self.ineligible[desc.replica_partition[r], desc.replica_broker[r]] = True
-
-    def brokers(self, p):
-        return self.dist[self.off[p]:self.off[p + 1]]
-
-    def legit(self, sources):
-        """GoalUtils.legitMove for every (source, broker) cell, the source broker itself excluded."""
-        out = np.zeros((len(sources), self.B), dtype=bool)
-        for i, (typ, p, src) in enumerate(sources):
-            if typ == MOVE:
-                out[i] = ~self.hosts[p] & ~self.ineligible[p]
-            elif self.leaders[p] == src:
-                out[i] = self.hosts[p]
-            out[i, src] = False
-        return out
+def legit_moves(pl, sources):
+    """GoalUtils.legitMove for every (source, broker) cell, the source broker itself excluded."""
+    out = np.zeros((len(sources), pl.B), dtype=bool)
+    for i, (typ, p, src) in enumerate(sources):
+        if typ == MOVE:
+            out[i] = ~pl.hosts[p] & ~pl.ineligible[p]
+        elif pl.leaders[p] == src:
+            out[i] = pl.hosts[p]
+        out[i, src] = False
+    return out
 
 
 def sample_sources(pl, rs, per_type):
@@ -102,29 +69,22 @@ def assert_same(got, want, sources, what=""):
     assert bad.size == 0, (what, [(sources[i], int(b), bool(got[i, b]), bool(want[i, b])) for i, b in bad[:10]])
 
 
-class Case:
+class Case(ChainCase):
     """A product session and an oracle cluster after the same chain, a sample of sources and the oracle's verdicts."""
 
     def __init__(self, lib, cluster_props, goals=DEFAULT_GOALS, bc=None, sources=None):
+        buf = ccmi.RandomCluster.generate(lib, **cluster_props)
+        super().__init__(lib, buf.desc, buf)
         self.goals = list(goals)
-        self.bc = bc or constraint(1.05, max_replicas=3000)
-        self.buf = ccmi.RandomCluster.generate(lib, **cluster_props)
-        self.cm = ccmi.ClusterModel.from_buffers(self.buf)
-        self.oc = OracleCluster.from_desc(self.buf.desc)
-        ccmi.GoalOptimizer(self.bc).optimizations(self.cm, ccmi.goals_from_names(self.goals))
-        self.oc.optimize(self.goals, self.bc)
-        assert self.cm.actions() == self.oc.actions()
+        self.optimize(self.goals, bc or constraint(1.05, max_replicas=3000))
         self.pl = self.placement()
         self.sources = sources(self) if sources else sample_sources(self.pl, np.random.RandomState(SEED), PER_TYPE)
         self.types = np.array([s[0] for s in self.sources])
-        self.legit = self.pl.legit(self.sources)
+        self.legit = legit_moves(self.pl, self.sources)
         self.accepts = oracle_accepts(self.oc, self.goals, self.sources, self.legit)
         self.all_goals = expected_mask(self.legit, self.accepts, range(len(self.goals)))
         for a in (self.legit, self.accepts, self.all_goals):
             a.setflags(write=False)
-
-    def placement(self):
-        return Placement(self.buf.desc, self.oc.replica_distribution(), self.oc.leader_distribution())
 
 
 @pytest.fixture(scope="module")
@@ -213,38 +173,14 @@ def test_gpu_more_goals_than_one_program(cases):
 
 
 # ------------------------------------------------------------------------------------------------ 4. chunk boundary
-_CHUNK_SCRIPT = r"""
-import json, sys
-import numpy as np
-sys.path.insert(0, {pkg!r}); sys.path.insert(0, {tests!r})
-import ccmi
-from parity import constraint
-lib = ccmi.Library.get({lib!r})
-buf = ccmi.RandomCluster.generate(lib, **{props!r})
-cm = ccmi.ClusterModel.from_buffers(buf)
-goals = list(ccmi.DEFAULT_GOALS)
-ccmi.GoalOptimizer(constraint(1.05, max_replicas=3000)).optimizations(cm, ccmi.goals_from_names(goals))
-src = [tuple(a) for a in json.load(open({sample!r}))]
-cm.reset_perf()
-got = cm.moves_acceptance_mask(goals, src)
-json.dump(dict(mask=got.tolist(), launches=cm.perf().accept_launches), open({out!r}, "w"))
-"""
-
-
 @pytest.mark.gpu
 def test_gpu_chunk_boundary_matches_oracle(cases, gpu_lib, tmp_path):
     """CCMI_MASK_CHUNK_SOURCES is read at session create: a fresh process with 4 answers n = 10 in 3 launches."""
     c = cases(130)
-    sample, out = tmp_path / "sample.json", tmp_path / "out.json"
-    json.dump(c.sources[:10], open(sample, "w"))
-    code = _CHUNK_SCRIPT.format(pkg=os.path.join(REPO, "cruise-control_amd"), tests=os.path.join(REPO, "tests"),
-                                lib=gpu_lib.path, props=props(130), sample=str(sample), out=str(out))
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, CCMI_MASK_CHUNK_SOURCES="4"),
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    res = json.load(open(out))
-    assert res["launches"] == 3
-    assert_same(np.array(res["mask"], dtype=bool), c.all_goals[:10], c.sources[:10])
+    mask, launches = run_in_fresh_process(gpu_lib, tmp_path, props(130), dict(CCMI_MASK_CHUNK_SOURCES="4"), c.sources[:10],
+                                          "cm.moves_acceptance_mask(goals, [tuple(a) for a in sample])")
+    assert launches == 3
+    assert_same(np.array(mask, dtype=bool), c.all_goals[:10], c.sources[:10])
 
 
 # ------------------------------------------------------------------------------------------------ 5. agreement with K9
@@ -290,7 +226,7 @@ def test_gpu_masks_after_session_apply_match_oracle(gpu_lib, oracle_lib):
     fresh = sample_sources(pl, np.random.RandomState(SEED + 1), 60)
     again += fresh
     assert any(s[2] in brokers for s in fresh)
-    legit = pl.legit(again)
+    legit = legit_moves(pl, again)
     accepts = oracle_accepts(c.oc, DEFAULT_GOALS, again, legit)
     # the moved replicas' old brokers are legit destinations again: the reference changed with the actions
     for typ, p, src, dst, *_ in external:
@@ -330,12 +266,8 @@ def test_gpu_ineligible_brokers_are_cleared(gpu_lib, oracle_lib):
 # ------------------------------------------------------------------------------------------------ 8. capacity goals
 @pytest.mark.gpu
 def test_gpu_capacity_goals_directed_sources(gpu_lib, oracle_lib):
-    from test_actions_acceptance import (CAPACITY_GOALS, CAPACITY_MIXED, CAPACITY_THRESHOLDS, Placement as ActionPlacement,
-                                         directed_capacity_actions)
-
     def sources(case):
-        pl = ActionPlacement(case.buf.desc, case.oc.replica_distribution(), case.oc.leader_distribution())
-        acts = directed_capacity_actions(case.buf.desc, pl, case.oc)
+        acts = directed_capacity_actions(case.desc, case.pl, case.oc)
         return sorted({(a[0], a[1], a[2]) for a in acts})
 
     bc = constraint(1.05, max_replicas=3000)
@@ -351,41 +283,33 @@ def test_gpu_capacity_goals_directed_sources(gpu_lib, oracle_lib):
 
 
 # ------------------------------------------------------------------------------------------------ 9. errors
-def _status_of(call):
-    try:
-        call()
-    except ccmi.CruiseControlError as e:
-        return type(e), getattr(e, "first_invalid", None)
-    return None, None
-
-
 @pytest.mark.gpu
 def test_gpu_errors_leave_the_session_untouched(cases):
     c = cases(20)
     cm, src = c.cm, c.sources[:9]
     logged = len(cm.actions())
     # a kind the session has not optimized; an intra-broker kind (16) is refused as such, optimized or not
-    assert _status_of(lambda: cm.moves_acceptance_mask(["RackAwareGoal", "RackAwareDistributionGoal"], src)) == \
+    assert status_of(lambda: cm.moves_acceptance_mask(["RackAwareGoal", "RackAwareDistributionGoal"], src)) == \
         (ccmi.IllegalArgumentException, -1)
     assert ccmi.GOAL_KINDS["IntraBrokerDiskCapacityGoal"] == 16
-    assert _status_of(lambda: cm.moves_acceptance_mask(["RackAwareGoal", "IntraBrokerDiskCapacityGoal"], src)) == \
+    assert status_of(lambda: cm.moves_acceptance_mask(["RackAwareGoal", "IntraBrokerDiskCapacityGoal"], src)) == \
         (ccmi.UnsupportedOperationException, -1)
-    assert _status_of(lambda: cm.moves_acceptance_mask(["IntraBrokerDiskUsageDistributionGoal"], [])) == \
+    assert status_of(lambda: cm.moves_acceptance_mask(["IntraBrokerDiskUsageDistributionGoal"], [])) == \
         (ccmi.UnsupportedOperationException, -1)
     # a swap is not a move source, at index 2 of 3
-    assert _status_of(lambda: cm.moves_acceptance_mask(DEFAULT_GOALS, src[:2] + [(SWAP,) + src[2][1:]])) == \
+    assert status_of(lambda: cm.moves_acceptance_mask(DEFAULT_GOALS, src[:2] + [(SWAP,) + src[2][1:]])) == \
         (ccmi.IllegalArgumentException, 2)
     # indices outside the model are refused before the device sees them
-    assert _status_of(lambda: cm.moves_acceptance_mask(DEFAULT_GOALS, [src[0], (MOVE, 10 ** 6, 0)])) == \
+    assert status_of(lambda: cm.moves_acceptance_mask(DEFAULT_GOALS, [src[0], (MOVE, 10 ** 6, 0)])) == \
         (ccmi.IllegalArgumentException, 1)
-    assert _status_of(lambda: cm.moves_acceptance_mask(DEFAULT_GOALS, [(MOVE, -1, 0)])) == \
+    assert status_of(lambda: cm.moves_acceptance_mask(DEFAULT_GOALS, [(MOVE, -1, 0)])) == \
         (ccmi.IllegalArgumentException, 0)
-    assert _status_of(lambda: cm.moves_acceptance_mask([], [(MOVE, src[0][1], 20)])) == \
+    assert status_of(lambda: cm.moves_acceptance_mask([], [(MOVE, src[0][1], 20)])) == \
         (ccmi.IllegalArgumentException, 0)
     # the source broker does not host the partition, at index 5 of 9
     p = src[5][1]
     stranger = next(b for b in range(20) if not c.pl.hosts[p, b])
-    assert _status_of(lambda: cm.moves_acceptance_mask(DEFAULT_GOALS, src[:5] + [(MOVE, p, stranger)] + src[6:])) == \
+    assert status_of(lambda: cm.moves_acceptance_mask(DEFAULT_GOALS, src[:5] + [(MOVE, p, stranger)] + src[6:])) == \
         (ccmi.IllegalArgumentException, 5)
     # a leadership source whose replica is not the leader: no legit destination, no error
     p = next(q for q in range(c.pl.P) if len(c.pl.brokers(q)) > 1)

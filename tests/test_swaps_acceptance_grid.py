@@ -9,63 +9,26 @@ cells legit both ways the full [n, m, G] matrix of OracleCluster.action_acceptan
 code of any goal list is the first non-zero verdict along that list. Every comparison is exact.
 """
 import ctypes as C
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import ccmi
-from oracle_binding import OracleCluster
+from acceptance_support import (ACCEPT, CANDIDATE_NOT_LEGIT, DEFAULT_GOALS, REPLICA_REJECT, SEED, SOURCE_NOT_LEGIT, SWAP,
+                                ChainCase, Placement, props, run_in_fresh_process, status_of)
 from parity import constraint
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEFAULT_GOALS = list(ccmi.DEFAULT_GOALS)
-SEED = 20261019
-SWAP = 2
-ACCEPT, REPLICA_REJECT, BROKER_REJECT, SOURCE_NOT_LEGIT, CANDIDATE_NOT_LEGIT = range(5)
-BAD_DISKS = ccmi.BROKER_STATES["BAD_DISKS"]
-
-
-def props(num_brokers, **more):
-    return dict(num_racks=5, num_brokers=num_brokers, num_replicas=6000, num_topics=300, **more)
 
 
 # ------------------------------------------------------------------------------------------------ the reference
-class Placement:
-    """Partition membership of a model (replica_distribution order) as a [P, B] matrix."""
-
-    def __init__(self, desc, dist):
-        self.B, self.P = desc.num_brokers, desc.num_partitions
-        self.off = list(desc.partition_offset[:self.P + 1])
-        self.dist = list(dist)
-        slot_part = np.repeat(np.arange(self.P), np.diff(self.off))
-        self.hosts = np.zeros((self.P, self.B), dtype=bool)
-        self.hosts[slot_part, self.dist] = True
-        # Partition._ineligibleBrokers: the BAD_DISKS brokers that held an offline replica of the partition (the desc)
-        self.ineligible = np.zeros((self.P, self.B), dtype=bool)
-        for r in range(desc.num_replicas):
-            if desc.replica_offline[r] and desc.broker_state[desc.replica_broker[r]] == BAD_DISKS:
-                self.ineligible[desc.replica_partition[r], desc.replica_broker[r]] = True
-
-    def brokers(self, p):
-        return self.dist[self.off[p]:self.off[p + 1]]
-
-    def replicas_on(self, b):
-        """Every replica of broker b as (partition, broker)."""
-        return [(int(p), int(b)) for p in np.flatnonzero(self.hosts[:, b])]
-
-    def legit(self, sources, candidates):
-        """[n, m] int8: 3 where legitMove(source, candidate's broker) fails, else 4 where legitMove(candidate, source's
-        broker) fails, else 0."""
-        src = np.array(sources, dtype=np.int64).reshape(-1, 2)
-        cand = np.array(candidates, dtype=np.int64).reshape(-1, 2)
-        closed = self.hosts | self.ineligible  # [p, b]: b is no destination of a replica of p
-        first = closed[src[:, 0][:, None], cand[:, 1][None, :]]
-        second = closed[cand[:, 0][None, :], src[:, 1][:, None]]
-        return np.where(first, SOURCE_NOT_LEGIT, np.where(second, CANDIDATE_NOT_LEGIT, ACCEPT)).astype(np.int8)
+def legit_swaps(pl, sources, candidates):
+    """[n, m] int8: 3 where legitMove(source, candidate's broker) fails, else 4 where legitMove(candidate, source's
+    broker) fails, else 0."""
+    src = np.array(sources, dtype=np.int64).reshape(-1, 2)
+    cand = np.array(candidates, dtype=np.int64).reshape(-1, 2)
+    closed = pl.hosts | pl.ineligible  # [p, b]: b is no destination of a replica of p
+    first = closed[src[:, 0][:, None], cand[:, 1][None, :]]
+    second = closed[cand[:, 0][None, :], src[:, 1][:, None]]
+    return np.where(first, SOURCE_NOT_LEGIT, np.where(second, CANDIDATE_NOT_LEGIT, ACCEPT)).astype(np.int8)
 
 
 def oracle_verdicts(oc, goals, sources, candidates, legit):
@@ -117,30 +80,23 @@ def sample_replicas(pl, rs, directed=False):
     return sources, candidates
 
 
-class Case:
+class Case(ChainCase):
     """A product session and an oracle cluster after the same chain, a grid of replicas and the oracle's verdicts."""
 
     def __init__(self, lib, cluster_props, goals=DEFAULT_GOALS, bc=None, replicas=None, directed=False):
+        buf = ccmi.RandomCluster.generate(lib, **cluster_props)
+        super().__init__(lib, buf.desc, buf)
         self.goals = list(goals)
-        self.bc = bc or constraint(1.05, max_replicas=3000)
-        self.buf = ccmi.RandomCluster.generate(lib, **cluster_props)
-        self.cm = ccmi.ClusterModel.from_buffers(self.buf)
-        self.oc = OracleCluster.from_desc(self.buf.desc)
-        ccmi.GoalOptimizer(self.bc).optimizations(self.cm, ccmi.goals_from_names(self.goals))
-        self.oc.optimize(self.goals, self.bc)
-        assert self.cm.actions() == self.oc.actions()
+        self.optimize(self.goals, bc or constraint(1.05, max_replicas=3000))
         self.pl = self.placement()
         self.sources, self.candidates = (replicas(self) if replicas else
                                          sample_replicas(self.pl, np.random.RandomState(SEED), directed))
         self.n, self.m = len(self.sources), len(self.candidates)
-        self.legit = self.pl.legit(self.sources, self.candidates)
+        self.legit = legit_swaps(self.pl, self.sources, self.candidates)
         self.verdicts = oracle_verdicts(self.oc, self.goals, self.sources, self.candidates, self.legit)
         self.all_goals = self.expected(self.goals)
         for a in (self.legit, self.verdicts, self.all_goals):
             a.setflags(write=False)
-
-    def placement(self):
-        return Placement(self.buf.desc, self.oc.replica_distribution())
 
     def expected(self, names):
         return expected_codes(self.legit, self.verdicts, [self.goals.index(g) for g in names])
@@ -249,40 +205,17 @@ def test_gpu_more_goals_than_one_program(cases):
 
 
 # ------------------------------------------------------------------------------------------------ 4. chunk boundary
-_CHUNK_SCRIPT = r"""
-import json, sys
-import numpy as np
-sys.path.insert(0, {pkg!r}); sys.path.insert(0, {tests!r})
-import ccmi
-from parity import constraint
-lib = ccmi.Library.get({lib!r})
-buf = ccmi.RandomCluster.generate(lib, **{props!r})
-cm = ccmi.ClusterModel.from_buffers(buf)
-goals = list(ccmi.DEFAULT_GOALS)
-ccmi.GoalOptimizer(constraint(1.05, max_replicas=3000)).optimizations(cm, ccmi.goals_from_names(goals))
-sample = json.load(open({sample!r}))
-cm.reset_perf()
-got = cm.swaps_acceptance_grid(goals, sample["sources"], sample["candidates"])
-json.dump(dict(codes=got.tolist(), launches=cm.perf().accept_launches), open({out!r}, "w"))
-"""
-
-
 @pytest.mark.gpu
 def test_gpu_chunk_boundary_matches_oracle(cases, gpu_lib, tmp_path):
     """CCMI_SWAP_CHUNK_CELLS is read at session create: a fresh process with 512 and m = 142 (a row of 192 bytes on the
     device, 2 sources per launch) answers n = 5 in 3 launches."""
     c = cases(130)
     src, cand = c.sources[:5], c.candidates[:142]
-    sample, out = tmp_path / "sample.json", tmp_path / "out.json"
-    json.dump(dict(sources=src, candidates=cand), open(sample, "w"))
-    code = _CHUNK_SCRIPT.format(pkg=os.path.join(REPO, "cruise-control_amd"), tests=os.path.join(REPO, "tests"),
-                                lib=gpu_lib.path, props=props(130), sample=str(sample), out=str(out))
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, CCMI_SWAP_CHUNK_CELLS="512"),
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    res = json.load(open(out))
-    assert res["launches"] == 3
-    assert_same(np.array(res["codes"], dtype=np.int8).reshape(5, 142), c.all_goals[:5, :142], src, cand)
+    codes, launches = run_in_fresh_process(gpu_lib, tmp_path, props(130), dict(CCMI_SWAP_CHUNK_CELLS="512"),
+                                           dict(sources=src, candidates=cand),
+                                           'cm.swaps_acceptance_grid(goals, sample["sources"], sample["candidates"])')
+    assert launches == 3
+    assert_same(np.array(codes, dtype=np.int8).reshape(5, 142), c.all_goals[:5, :142], src, cand)
 
 
 # ------------------------------------------------------------------------------------------------ 5. agreement with K9
@@ -326,7 +259,7 @@ def test_gpu_grid_after_session_apply_matches_oracle(gpu_lib, oracle_lib):
     assert len(brokers) >= 2
     sources = moved + [pl.replicas_on(b)[0] for b in brokers] + fresh_src[:8]
     candidates = moved + [r for b in brokers for r in pl.replicas_on(b)[:30]] + fresh_cand[:200]
-    legit = pl.legit(sources, candidates)
+    legit = legit_swaps(pl, sources, candidates)
     verdicts = oracle_verdicts(c.oc, DEFAULT_GOALS, sources, candidates, legit)
     # a swapped replica's old broker no longer hosts its partition: the replica that took its place there is no code-3
     # candidate for it any more, and the reference changed with the swaps
@@ -379,15 +312,11 @@ def test_gpu_shared_hosts_match_oracle(gpu_lib, oracle_lib):
     from test_hosts import HOST_GOALS, SHARED, _model
 
     flat = _model(SHARED)
-    cm = ccmi.ClusterModel(flat.desc, device=0, lib=gpu_lib, keepalive=flat)
-    oc = OracleCluster.from_desc(flat.desc)
-    bc = ccmi.BalancingConstraint()
-    ccmi.GoalOptimizer(bc).optimizations(cm, ccmi.goals_from_names(HOST_GOALS))
-    oc.optimize(HOST_GOALS, bc)
-    assert cm.actions() == oc.actions()
-    pl = Placement(flat.desc, oc.replica_distribution())
+    c = ChainCase(gpu_lib, flat.desc, flat)
+    c.optimize(HOST_GOALS, ccmi.BalancingConstraint())
+    cm, oc, pl = c.cm, c.oc, c.placement()
     every = [r for b in range(pl.B) for r in pl.replicas_on(b)]
-    legit = pl.legit(every, every)
+    legit = legit_swaps(pl, every, every)
     verdicts = oracle_verdicts(oc, HOST_GOALS, every, every, legit)
     want = expected_codes(legit, verdicts, range(len(HOST_GOALS)))
     assert (want == ACCEPT).any() and (want == REPLICA_REJECT).any()
@@ -397,14 +326,6 @@ def test_gpu_shared_hosts_match_oracle(gpu_lib, oracle_lib):
 
 
 # ------------------------------------------------------------------------------------------------ 9. errors
-def _status_of(call):
-    try:
-        call()
-    except ccmi.CruiseControlError as e:
-        return type(e), getattr(e, "first_invalid", None)
-    return None, None
-
-
 @pytest.mark.gpu
 def test_gpu_errors_leave_the_session_untouched(cases):
     c = cases(20)
@@ -412,40 +333,40 @@ def test_gpu_errors_leave_the_session_untouched(cases):
     n = len(src)
     logged = len(cm.actions())
     # a kind the session has not optimized; an intra-broker kind (16, 17) is refused as such, optimized or not
-    assert _status_of(lambda: cm.swaps_acceptance_grid(["RackAwareGoal", "RackAwareDistributionGoal"], src, cand)) == \
+    assert status_of(lambda: cm.swaps_acceptance_grid(["RackAwareGoal", "RackAwareDistributionGoal"], src, cand)) == \
         (ccmi.IllegalArgumentException, -1)
-    assert _status_of(lambda: cm.swaps_acceptance_grid(["RackAwareDistributionGoal"], [], [])) == \
+    assert status_of(lambda: cm.swaps_acceptance_grid(["RackAwareDistributionGoal"], [], [])) == \
         (ccmi.IllegalArgumentException, -1)
     assert ccmi.GOAL_KINDS["IntraBrokerDiskCapacityGoal"] == 16
     assert ccmi.GOAL_KINDS["IntraBrokerDiskUsageDistributionGoal"] == 17
-    assert _status_of(lambda: cm.swaps_acceptance_grid(["RackAwareGoal", "IntraBrokerDiskCapacityGoal"], src, cand)) == \
+    assert status_of(lambda: cm.swaps_acceptance_grid(["RackAwareGoal", "IntraBrokerDiskCapacityGoal"], src, cand)) == \
         (ccmi.UnsupportedOperationException, -1)
-    assert _status_of(lambda: cm.swaps_acceptance_grid(["IntraBrokerDiskUsageDistributionGoal"], [], [])) == \
+    assert status_of(lambda: cm.swaps_acceptance_grid(["IntraBrokerDiskUsageDistributionGoal"], [], [])) == \
         (ccmi.UnsupportedOperationException, -1)
-    assert _status_of(lambda: cm.swaps_acceptance_grid(["IntraBrokerDiskUsageDistributionGoal"], src, [])) == \
+    assert status_of(lambda: cm.swaps_acceptance_grid(["IntraBrokerDiskUsageDistributionGoal"], src, [])) == \
         (ccmi.UnsupportedOperationException, -1)
     # indices outside the model are refused before the device sees them: i for a source, n + j for a candidate
-    assert _status_of(lambda: cm.swaps_acceptance_grid(DEFAULT_GOALS, [src[0], (10 ** 6, 0)], cand)) == \
+    assert status_of(lambda: cm.swaps_acceptance_grid(DEFAULT_GOALS, [src[0], (10 ** 6, 0)], cand)) == \
         (ccmi.IllegalArgumentException, 1)
-    assert _status_of(lambda: cm.swaps_acceptance_grid(DEFAULT_GOALS, [(-1, 0)], cand)) == \
+    assert status_of(lambda: cm.swaps_acceptance_grid(DEFAULT_GOALS, [(-1, 0)], cand)) == \
         (ccmi.IllegalArgumentException, 0)
-    assert _status_of(lambda: cm.swaps_acceptance_grid([], [(src[0][0], 20)], cand)) == \
+    assert status_of(lambda: cm.swaps_acceptance_grid([], [(src[0][0], 20)], cand)) == \
         (ccmi.IllegalArgumentException, 0)
-    assert _status_of(lambda: cm.swaps_acceptance_grid([], src, [cand[0], (cand[1][0], -1)])) == \
+    assert status_of(lambda: cm.swaps_acceptance_grid([], src, [cand[0], (cand[1][0], -1)])) == \
         (ccmi.IllegalArgumentException, n + 1)
-    assert _status_of(lambda: cm.swaps_acceptance_grid(DEFAULT_GOALS, src, cand[:3] + [(c.pl.P, 0)])) == \
+    assert status_of(lambda: cm.swaps_acceptance_grid(DEFAULT_GOALS, src, cand[:3] + [(c.pl.P, 0)])) == \
         (ccmi.IllegalArgumentException, n + 3)
     # a broker that does not hold the partition: the source at index 2, the candidate at j = 5
     p = src[2][0]
     stranger = next(b for b in range(20) if not c.pl.hosts[p, b])
-    assert _status_of(lambda: cm.swaps_acceptance_grid(DEFAULT_GOALS, src[:2] + [(p, stranger)] + src[3:], cand)) == \
+    assert status_of(lambda: cm.swaps_acceptance_grid(DEFAULT_GOALS, src[:2] + [(p, stranger)] + src[3:], cand)) == \
         (ccmi.IllegalArgumentException, 2)
     q = cand[5][0]
     stranger = next(b for b in range(20) if not c.pl.hosts[q, b])
-    assert _status_of(lambda: cm.swaps_acceptance_grid(DEFAULT_GOALS, src, cand[:5] + [(q, stranger)] + cand[6:])) == \
+    assert status_of(lambda: cm.swaps_acceptance_grid(DEFAULT_GOALS, src, cand[:5] + [(q, stranger)] + cand[6:])) == \
         (ccmi.IllegalArgumentException, n + 5)
     # both bad: the sources are checked first
-    assert _status_of(lambda: cm.swaps_acceptance_grid(DEFAULT_GOALS, src[:1] + [(-1, 0)], [(q, stranger)])) == \
+    assert status_of(lambda: cm.swaps_acceptance_grid(DEFAULT_GOALS, src[:1] + [(-1, 0)], [(q, stranger)])) == \
         (ccmi.IllegalArgumentException, 1)
     # the session is as it was and still answers
     assert len(cm.actions()) == logged
@@ -466,7 +387,7 @@ def test_gpu_terminal_goal_is_a_state_error(gpu_lib):
     with pytest.raises(ccmi.IllegalStateException):
         cm.swaps_acceptance_grid(ka, src, cand)
     assert cm.swaps_acceptance_grid(ka, src, []).shape == (3, 0)
-    legit = pl.legit(src, cand)
+    legit = legit_swaps(pl, src, cand)
     assert (legit == ACCEPT).any()
     got = cm.swaps_acceptance_grid(ka[:1], src, cand)
     assert ((got >= SOURCE_NOT_LEGIT) == (legit != ACCEPT)).all() and (got[legit != ACCEPT] == legit[legit != ACCEPT]).all()
