@@ -204,6 +204,18 @@ class DiskStatsStruct(C.Structure):  # ccmi_disk_stats: one disk's DiskStats, 40
                 ("broker", C.c_int32)]
 
 
+class PartitionLoadQueryStruct(C.Structure):  # ccmi_partition_load_query, 64 bytes
+    _fields_ = [("resource", C.c_int32), ("want_max_load", C.c_int32), ("want_avg_load", C.c_int32),
+                ("entries", C.c_int32), ("partition_lower", C.c_int32), ("partition_upper", C.c_int32),
+                ("reserved", C.c_int32 * 4), ("topic_selected", C.POINTER(C.c_uint8)),
+                ("broker_selected", C.POINTER(C.c_uint8)), ("tie_rank", C.POINTER(C.c_int32))]
+
+
+class PartitionLoadRecordStruct(C.Structure):  # ccmi_partition_load_record, 80 bytes
+    _fields_ = [("util", C.c_double * 4), ("partition", C.c_int32), ("num_replicas", C.c_int32),
+                ("brokers", C.c_int32 * 8), ("reserved", C.c_int32 * 2)]
+
+
 # ----------------------------------------------------------------------------------------------- errors
 class CruiseControlError(RuntimeError):
     pass
@@ -239,7 +251,7 @@ EXPORTED_SYMBOLS = (
     "ccmi_session_destroy", "ccmi_optimizations", "ccmi_goal_optimize", "ccmi_action_acceptance",
     "ccmi_action_acceptance_by_kind", "ccmi_actions_acceptance", "ccmi_moves_acceptance_mask", "ccmi_swaps_acceptance_grid",
     "ccmi_session_apply", "ccmi_last_failure_provision",
-    "ccmi_compute_cluster_stats", "ccmi_broker_stats", "ccmi_action_log_count", "ccmi_action_log_copy", "ccmi_replica_distribution",
+    "ccmi_compute_cluster_stats", "ccmi_broker_stats", "ccmi_partition_load", "ccmi_action_log_count", "ccmi_action_log_copy", "ccmi_replica_distribution",
     "ccmi_leader_distribution", "ccmi_replica_disks", "ccmi_proposal_count", "ccmi_proposals",
     "ccmi_proposal_disks", "ccmi_perf", "ccmi_perf_reset",
     "ccmi_set_kernel_timing", "ccmi_session_set_shard", "ccmi_rccl_unique_id", "ccmi_session_attach_rccl",
@@ -297,6 +309,10 @@ class Library:
         self.has_broker_stats = hasattr(L, "ccmi_broker_stats")
         if self.has_broker_stats:
             L.ccmi_broker_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
+        self.has_partition_load = hasattr(L, "ccmi_partition_load")
+        if self.has_partition_load:
+            L.ccmi_partition_load.argtypes = [C.c_void_p, C.POINTER(PartitionLoadQueryStruct), C.c_void_p,
+                                              C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.ccmi_session_apply.argtypes = [C.c_void_p, C.POINTER(ActionStruct), C.c_int64, C.POINTER(C.c_int64)]
         L.ccmi_last_failure_provision.argtypes = [C.c_void_p, C.POINTER(ProvisionRespStruct)]
         L.ccmi_compute_cluster_stats.argtypes = [C.c_void_p, C.POINTER(ConstraintStruct), C.POINTER(OptionsStruct),
@@ -731,6 +747,45 @@ class BrokerStats:
     def __eq__(self, other) -> bool:
         return (isinstance(other, BrokerStats) and self.brokers.tobytes() == other.brokers.tobytes()
                 and self.hosts.tobytes() == other.hosts.tobytes() and self.disks.tobytes() == other.disks.tobytes())
+
+    __hash__ = None
+
+
+class PartitionLoadState:
+    """servlet/response/PartitionLoadState.java as PartitionLoadRunnable.getResult fills it, computed, sorted and cut by
+    ccmi_partition_load. `records` is a numpy structured array with the fields of PartitionLoadRecordStruct, in the
+    response's order; `num_selected` the partitions the selection kept before the entries cut. MESSAGE_IN_RATE (msg_in)
+    is not a metric the model carries and is left out; the plain-text table is left to the servlet."""
+
+    JSON_VERSION = 1
+    RESOURCE_KEYS = (("cpu", 0), ("networkInbound", 1), ("networkOutbound", 2), ("disk", 3))  # Resource.resource()
+
+    def __init__(self, records, num_selected: int, topic_names: Sequence[str], partition_topic: Sequence[int],
+                 partition_number: Sequence[int], broker_ids: Sequence[int]):
+        self.records = records
+        self.num_selected = int(num_selected)
+        self.topic_names = list(topic_names)
+        self.partition_topic, self.partition_number = partition_topic, partition_number
+        self.broker_ids = list(broker_ids)
+
+    def get_json_structure(self) -> Dict[str, object]:
+        """PartitionLoadState.getJsonString (PartitionLoadState.java:103-150): leader and followers as broker ids,
+        `partition` the topic's partition number."""
+        out = []
+        for r in self.records:
+            p, n = int(r["partition"]), int(r["num_replicas"])
+            e: Dict[str, object] = {"topic": self.topic_names[self.partition_topic[p]],
+                                    "partition": int(self.partition_number[p]),
+                                    "leader": self.broker_ids[int(r["brokers"][0])],
+                                    "followers": [self.broker_ids[int(b)] for b in r["brokers"][1:n]]}
+            for key, res in self.RESOURCE_KEYS:
+                e[key] = float(r["util"][res])
+            out.append(e)
+        return {"version": self.JSON_VERSION, "records": out}
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, PartitionLoadState) and self.num_selected == other.num_selected
+                and self.records.tobytes() == other.records.tobytes())
 
     __hash__ = None
 
@@ -1402,6 +1457,58 @@ class ClusterModel:
         racks, host_names = self.stats_names()
         logdirs = [self.desc.disk_logdir[d].decode() for d in range(D)]
         return BrokerStats(brokers, hosts[:nh.value].copy(), disks, self.broker_ids(), racks, host_names, logdirs)
+
+    def partition_load(self, resource: str = "DISK", max_load: bool = False, avg_load: bool = False,
+                       entries: int = 2**31 - 1, topic: Optional[str] = None,
+                       partition_range: Optional[Sequence[int]] = None, broker_ids: Iterable[int] = (),
+                       tie_rank=None) -> "PartitionLoadState":
+        """The partition load response (PartitionLoadRunnable.getResult) of the session's current model in one device
+        call (ccmi_partition_load): the partitions ordered by the utilization of `resource` on their current leader,
+        descending. `topic` is a regex that must match the whole topic name (Pattern.matcher().matches()),
+        `partition_range` = (lower, upper) partition numbers, both inclusive, `broker_ids` the Kafka ids of which a
+        kept partition has at least one among its current brokers (empty: every partition). `tie_rank[p]` orders
+        partitions with exactly equal keys (the reference's HashMap iteration order, which the caller holds); None is
+        the partition index. The session is not changed."""
+        import re
+
+        import numpy as np
+
+        if not self.lib.has_partition_load:
+            raise UnsupportedOperationException(
+                f"{self.lib.path} does not export ccmi_partition_load: the response is computed on the device only")
+        d = self.desc
+        P, T, B = d.num_partitions, d.num_topics, d.num_brokers
+        q = PartitionLoadQueryStruct()
+        q.resource = resource if isinstance(resource, int) else RESOURCES.index(resource)
+        q.want_max_load, q.want_avg_load = int(bool(max_load)), int(bool(avg_load))
+        q.entries = int(entries)
+        lower, upper = partition_range if partition_range is not None else (-2**31, 2**31 - 1)
+        q.partition_lower, q.partition_upper = int(lower), int(upper)
+        keep = []
+        if topic is not None:
+            pat = re.compile(topic)
+            sel = np.array([1 if pat.fullmatch(n) else 0 for n in self.topic_names()], dtype=np.uint8)
+            keep.append(sel)
+            q.topic_selected = sel.ctypes.data_as(C.POINTER(C.c_uint8))
+        wanted = set(int(b) for b in broker_ids)
+        ids = self.broker_ids()
+        if wanted:
+            sel = np.array([1 if ids[b] in wanted else 0 for b in range(B)], dtype=np.uint8)
+            keep.append(sel)
+            q.broker_selected = sel.ctypes.data_as(C.POINTER(C.c_uint8))
+        if tie_rank is not None:
+            rank = np.ascontiguousarray(tie_rank, dtype=np.int32)
+            if rank.shape != (P,):
+                raise IllegalArgumentException(f"tie_rank needs one entry per partition ({P})")
+            keep.append(rank)
+            q.tie_rank = rank.ctypes.data_as(C.POINTER(C.c_int32))
+        records = np.zeros(max(0, min(q.entries, P)), dtype=np.dtype(PartitionLoadRecordStruct))
+        nrec, nsel = C.c_int64(0), C.c_int64(0)
+        self._checked(self.lib.lib.ccmi_partition_load(self.handle, C.byref(q), records.ctypes.data if len(records) else None,
+                                                       C.byref(nrec), C.byref(nsel)))
+        return PartitionLoadState(records[:nrec.value], nsel.value, self.topic_names(),
+                                  np.ctypeslib.as_array(d.partition_topic, shape=(P,)).copy() if P else [],
+                                  np.ctypeslib.as_array(d.partition_number, shape=(P,)).copy() if P else [], ids)
 
     def apply(self, actions) -> int:
         """Apply actions decided elsewhere (tuples in the action-log layout: type, partition, source,

@@ -294,6 +294,9 @@ Device::~Device() {
   for (void* p : statsRowAllocs_)  // brokerStats (device_accept.cpp)
     if (p) (void)hipFree(p);
   if (dStatMembers_) (void)hipFree(dStatMembers_);
+  for (void* p : plAllocs_)  // partitionLoad (device_accept.cpp)
+    if (p) (void)hipFree(p);
+  if (dPlOut_) (void)hipFree(dPlOut_);
   if (hStage_) (void)hipHostFree(hStage_);
   if (hResult_) (void)hipHostFree(hResult_);
   if (ev0_) (void)hipEventDestroy(EV0);

@@ -22,6 +22,7 @@
 
 struct ccmi_basic_stats;  // include/ccmi.h
 struct ccmi_disk_stats;
+struct ccmi_partition_load_record;
 
 namespace ccmi {
 
@@ -288,6 +289,19 @@ class Device {
   void brokerStats(ccmi_basic_stats* brokers, ccmi_basic_stats* hosts, ccmi_disk_stats* disks, const DiskMember* members,
                    int64_t nMembers, uint64_t memberVer);
 
+  // K13 (kernels/partition_load.hip, device_accept.cpp): the partition load response from the resident tables: every
+  // selected partition ordered by (utilization of q.resource on its current leader descending, tieRank ascending,
+  // partition ascending), the first min(q.entries, selected) as records. uploadPartitionNumbers once per session
+  // (TopicPartition.partition() of every partition). partitionLoad: the pending row updates and the pending chain
+  // loads (lrows / srows, syncChainLoads) reach the tables first; topicSel[T], brokerSel[B], tieRank[P] may each be
+  // null; records has room for min(q.entries, P) rows. A hand-written LSD radix sort on the device; the sort buffers are
+  // allocated on first use. Two stream syncs (the counts, then the rows) and one D2H copy of the returned rows. Counts
+  // into perf.statsLaunches / statsKernelMs / statsBytes. Not in the test emulation.
+  bool partitionNumbersUploaded() const { return dPlNumber_ != nullptr; }
+  void uploadPartitionNumbers(const int32_t* pNumber);
+  void partitionLoad(const PlQuery& q, const uint8_t* topicSel, const uint8_t* brokerSel, const int32_t* tieRank,
+                     ccmi_partition_load_record* records, int64_t* numRecords, int64_t* numSelected);
+
   // Disks (JBOD): the static disk / replica tables once per session; setDiskUtil whenever the host changed a disk's
   // utilization; intraRun = one intra-broker goal (K6); statsDisks = the disk part of ClusterModelStats.
   void uploadDisks(int D, const int32_t* bDiskOff, const int32_t* bDisks, const double* dCap, const uint8_t* dAlive,
@@ -440,6 +454,18 @@ class Device {
   uint64_t statMemberVer_ = 0;
   int statH_ = 0;
   std::vector<void*> statsRowAllocs_;
+  // partitionLoad: the static partition numbers, the query's arrays, the ping-pong sort buffers [P] each, the
+  // [256 x tiles] digit counts, the query state and the output rows (grown to the largest request so far)
+  int32_t *dPlNumber_ = nullptr, *dPlRank_ = nullptr;
+  uint8_t *dPlTopicSel_ = nullptr, *dPlBrokerSel_ = nullptr;
+  PlEntry* dPlBuf_[2] = {nullptr, nullptr};
+  uint32_t* dPlCounts_ = nullptr;
+  PlState* dPlState_ = nullptr;
+  ccmi_partition_load_record* dPlOut_ = nullptr;
+  size_t plOutCap_ = 0;
+  std::vector<void*> plAllocs_;
+  // the pending chain loads (lrows / srows) go to the device's Java loads and slot order outside a chain
+  void syncChainLoads();
   int32_t* dRackRes_ = nullptr;  // rackRowsGroups results (+ the evaluated-candidate counter after them)
   size_t rackResCap_ = 0;
   int32_t* dChainReq_ = nullptr;  // SOP_CHAIN request copy in HBM (the chain rereads it per decision)

@@ -1,8 +1,9 @@
 // Device::acceptBatch, Device::maskBatch and Device::swapGridBatch (device.h): the launchers of K9 accept_actions
 // (kernels/accept.hip), K10 accept_mask (kernels/accept_mask.hip) and K11 accept_swaps (kernels/accept_swap.hip), which
 // share one chunk protocol (Device::acceptChunk); and Device::brokerStats, the launcher of K12
-// (kernels/broker_stats.hip), which shares its scope and timing. A translation unit of its own, linked into libccmi.so
-// only: the test emulation of Device has none of these kernels.
+// (kernels/broker_stats.hip), and Device::partitionLoad, the launcher of K13 (kernels/partition_load.hip), which share
+// its scope and timing. A translation unit of its own, linked into libccmi.so only: the test emulation of Device has
+// none of these kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,6 +31,11 @@ hipError_t launchBrokerStatsHosts(const ccmi_basic_stats* rows, const int32_t* h
                                   const int32_t* hIdx, int H, int B, ccmi_basic_stats* out, hipStream_t st);
 hipError_t launchBrokerStatsDisks(const DiskMember* members, int64_t E, const ReplicaRec* replicas, int R, int D,
                                   ccmi_disk_stats* diskOut, hipStream_t st);
+hipError_t launchSyncLoads(const ChainTables& C, const LoadRow* lrows, int nl, const SlotRow* srows, int ns,
+                           hipStream_t st);
+hipError_t launchPartitionLoad(const PlTables& T, const PlQuery& q, PlState* st, PlEntry* bufA, PlEntry* bufB,
+                               uint32_t* counts, int tiles, int slots, ccmi_partition_load_record* out, int cap,
+                               int* launches, hipStream_t stream);
 
 namespace {
 constexpr double kAcceptWaitSeconds = 120.0;
@@ -242,6 +248,123 @@ void Device::brokerStats(ccmi_basic_stats* brokers, ccmi_basic_stats* hosts, ccm
   perf.statsBytes += (int64_t)B_ * (int64_t)(sizeof(BrokerRec) + sizeof(BrokerStatic) + sizeof(ccmi_basic_stats)) +
                      (hosts ? (int64_t)B_ * (int64_t)sizeof(ccmi_basic_stats) + (int64_t)statH_ * 136 : 0) +
                      (withDisks ? (int64_t)D_ * (16 + 4 + (int64_t)sizeof(ccmi_disk_stats)) + statMembers_ * 12 : 0);
+  addKernelMs(perf.statsKernelMs);
+}
+
+void Device::uploadPartitionNumbers(const int32_t* pNumber) {
+  DeviceGuard cur(ordinal_);
+  stopServer();
+  if (dPlNumber_) throw std::logic_error("uploadPartitionNumbers: once per session");
+  if (P_ < 1 || !pNumber) throw std::logic_error("uploadPartitionNumbers: arguments");
+  int32_t* d = nullptr;
+  hipCheck(hipMalloc((void**)&d, (size_t)P_ * sizeof(int32_t)), "hipMalloc partition numbers");
+  plAllocs_.push_back(d);
+  hipCheck(hipMemcpy(d, pNumber, (size_t)P_ * sizeof(int32_t), hipMemcpyHostToDevice), "upload partition numbers");
+  dPlNumber_ = d;
+}
+
+// What stageChainCopy does in front of a chain, without a request: the load and slot rows behind the staged row
+// updates, sync_loads, then prep for the row updates.
+void Device::syncChainLoads() {
+  if (!dRLoad_) throw std::runtime_error("device chain state not uploaded");
+  const size_t nl = lrows.size(), ns = srows.size();
+  const bool rows = !brows.empty() || !rrows.empty() || !prows.empty() || !tdeltas.empty();
+  if (!nl && !ns && !rows) return;
+  const size_t oS = (nl * sizeof(LoadRow) + 15) & ~(size_t)15;
+  const Staged g = packUpdates(oS + ns * sizeof(SlotRow) + 16);
+  if (nl) std::memcpy(hStage_ + g.end, lrows.data(), nl * sizeof(LoadRow));
+  if (ns) std::memcpy(hStage_ + g.end + oS, srows.data(), ns * sizeof(SlotRow));
+  hipCheck(launchSyncLoads(chainTables(), (const LoadRow*)(hStageDev_ + g.end), (int)nl,
+                           (const SlotRow*)(hStageDev_ + g.end + oS), (int)ns, (hipStream_t)st_),
+           "sync_loads");
+  lrows.clear();
+  srows.clear();
+  launchPrepFor(g, 0, false);
+}
+
+void Device::partitionLoad(const PlQuery& q, const uint8_t* topicSel, const uint8_t* brokerSel, const int32_t* tieRank,
+                           ccmi_partition_load_record* records, int64_t* numRecords, int64_t* numSelected) {
+  PlainLaunch call(*this);
+  if (!dPlNumber_) throw std::logic_error("partitionLoad before uploadPartitionNumbers");
+  if (!numRecords || q.entries < 0 || q.resource < 0 || q.resource > 3 || q.mode < 0 || q.mode > 2)
+    throw std::logic_error("partitionLoad: arguments");
+  const int cap = std::min(q.entries, P_);
+  if (cap > 0 && !records) throw std::logic_error("partitionLoad: no room for the records");
+  const hipStream_t st = (hipStream_t)st_;
+  const int tiles = (P_ + kPlSortTile - 1) / kPlSortTile;
+  if (!dPlState_) {  // first use: the query arrays, the sort buffers, the digit counts, the state
+    auto get = [&](auto** d, size_t n, const char* what) {
+      hipCheck(hipMalloc((void**)d, std::max<size_t>(1, n) * sizeof(**d)), what);
+      plAllocs_.push_back(*d);
+    };
+    get(&dPlRank_, (size_t)P_, "hipMalloc tie ranks");
+    get(&dPlTopicSel_, (size_t)T_, "hipMalloc topic mask");
+    get(&dPlBrokerSel_, (size_t)B_, "hipMalloc broker mask");
+    get(&dPlBuf_[0], (size_t)P_, "hipMalloc sort buffer");
+    get(&dPlBuf_[1], (size_t)P_, "hipMalloc sort buffer");
+    get(&dPlCounts_, (size_t)256 * (size_t)tiles, "hipMalloc digit counts");
+    get(&dPlState_, 1, "hipMalloc partition load state");  // last: marks the first use done
+  }
+  if ((size_t)cap > plOutCap_) {
+    if (dPlOut_) hipCheck(hipFree(dPlOut_), "hipFree");
+    dPlOut_ = nullptr;
+    plOutCap_ = 0;
+    hipCheck(hipMalloc((void**)&dPlOut_, (size_t)cap * sizeof(ccmi_partition_load_record)), "hipMalloc load records");
+    plOutCap_ = (size_t)cap;
+  }
+  // the device's tables current: the pending row updates (prep) and the pending chain loads (sync_loads)
+  syncChainLoads();
+  if (topicSel)
+    hipCheck(hipMemcpyAsync(dPlTopicSel_, topicSel, (size_t)T_, hipMemcpyHostToDevice, st), "upload topic mask");
+  if (brokerSel)
+    hipCheck(hipMemcpyAsync(dPlBrokerSel_, brokerSel, (size_t)B_, hipMemcpyHostToDevice, st), "upload broker mask");
+  if (tieRank)
+    hipCheck(hipMemcpyAsync(dPlRank_, tieRank, (size_t)P_ * sizeof(int32_t), hipMemcpyHostToDevice, st),
+             "upload tie ranks");
+  PlTables T;
+  T.parts = parts_;
+  T.replicas = replicas_;
+  T.rLoad = dRLoad_;
+  T.pLeader = dPLeader_;
+  T.pNumber = dPlNumber_;
+  T.topicSel = topicSel ? dPlTopicSel_ : nullptr;
+  T.brokerSel = brokerSel ? dPlBrokerSel_ : nullptr;
+  T.tieRank = tieRank ? dPlRank_ : nullptr;
+  T.B = B_;
+  T.R = R_;
+  T.P = P_;
+  T.T = T_;
+  T.W = W_;
+  // the most passes the query can need: the left-out flag only under a selection, the rank digits only with ranks
+  const bool selects = topicSel || brokerSel || q.lower > INT32_MIN || q.upper < INT32_MAX;
+  const int slots = (selects ? 1 : 0) + 8 + (tieRank ? 4 : 0);
+  int launches = 0;
+  timedLaunch([&] {
+    hipCheck(launchPartitionLoad(T, q, dPlState_, dPlBuf_[0], dPlBuf_[1], dPlCounts_, tiles, slots, dPlOut_, cap,
+                                 &launches, st),
+             "partition_load");
+  });
+  uint32_t head[2] = {0, 0};  // PlState.nKept, nRecords
+  hipCheck(hipMemcpyAsync(head, dPlState_, sizeof(head), hipMemcpyDeviceToHost, st), "D2H partition load counts");
+  streamWait("partition_load", kAcceptWaitSeconds);
+  perf.syncs++;
+  const int64_t nrec = std::min<int64_t>(head[1], cap);
+  if (nrec > 0) {
+    hipCheck(hipMemcpyAsync(records, dPlOut_, (size_t)nrec * sizeof(ccmi_partition_load_record), hipMemcpyDeviceToHost,
+                            st),
+             "D2H load records");
+    streamWait("partition_load records", kAcceptWaitSeconds);
+    perf.syncs++;
+  }
+  *numRecords = nrec;
+  if (numSelected) *numSelected = (int64_t)head[0];
+  // a statistics read-back, as brokerStats: per partition its record, leader id, number and LoadVec in and an entry
+  // out; per launched pass slot an entry in and out twice at most; per returned record the same reads and a row out
+  perf.statsLaunches += launches;
+  perf.statsBytes += (int64_t)P_ * (int64_t)(sizeof(PartitionRec) + 8 + sizeof(LoadVec) + sizeof(PlEntry)) +
+                     (int64_t)slots * (int64_t)P_ * 3 * (int64_t)sizeof(PlEntry) +
+                     nrec * (int64_t)(sizeof(PlEntry) + sizeof(PartitionRec) + sizeof(LoadVec) +
+                                      sizeof(ccmi_partition_load_record));
   addKernelMs(perf.statsKernelMs);
 }
 

@@ -251,6 +251,42 @@ struct DiskMember {
   int32_t replica, disk;
 };
 
+// ccmi_partition_load (kernels/partition_load.hip). PlEntry: one partition in the sort, 96 sort bits ascending — the
+// key is the utilization's bits ^ 0x7fff... (all ones for a partition the selection left out), the rank the caller's
+// tie rank (or the partition index) with its sign bit flipped. PlState: the device words of one query — the kept count,
+// the records to return, the OR of the kept entries' sort bits and of their complements {rank, key low, key high}, and
+// the plan: pass i sorts the first passN[i] entries on (composite >> passOff[i]) & passMask[i].
+constexpr int kPlSortTile = 2048;  // entries per workgroup of a sort pass
+constexpr int kPlMaxPasses = 13;   // the left-out flag, 8 key digits, 4 rank digits
+struct alignas(16) PlEntry {
+  uint64_t key;
+  uint32_t rank;
+  int32_t p;
+};
+static_assert(sizeof(PlEntry) == 16, "PlEntry is one 16-byte load");
+struct PlState {
+  uint32_t nKept, nRecords, nPass, pad;
+  uint32_t orBits[3], nandBits[3];
+  uint32_t passOff[kPlMaxPasses], passMask[kPlMaxPasses], passN[kPlMaxPasses];
+};
+struct PlQuery {
+  int32_t resource;      // Res
+  int32_t mode;          // 0: expectedUtilizationFor(res, false, false); 1: wantMaxLoad; 2: wantAvgLoad
+  int32_t entries;       // >= 0
+  int32_t lower, upper;  // partition number bounds, both inclusive
+};
+struct PlTables {
+  const PartitionRec* parts;
+  const ReplicaRec* replicas;
+  const LoadVec* rLoad;        // [R] Replica.load() (the chain tables' copy)
+  const int32_t* pLeader;      // [P] the leader's replica id
+  const int32_t* pNumber;      // [P] TopicPartition.partition() (static)
+  const uint8_t* topicSel;     // [T] or null
+  const uint8_t* brokerSel;    // [B] or null
+  const int32_t* tieRank;      // [P] or null
+  int32_t B, R, P, T, W;
+};
+
 struct UpdateList {
   const BrokerRow* brows;
   const ReplicaRow* rrows;

@@ -21,6 +21,9 @@
  *                                 analyzer/goals/AbstractGoal.java:287-338 (one code per replica pair)
  *   ccmi_broker_stats          <- ClusterModel.brokerStats(KafkaCruiseControlConfig)  model/ClusterModel.java:1303-1309
  *                                 (the load block of a rebalance response and of the load endpoint)
+ *   ccmi_partition_load        <- PartitionLoadRunnable.getResult  servlet/handler/async/runnable/PartitionLoadRunnable.java:32-60
+ *                                 -> ClusterModel.replicasSortedByUtilization model/ClusterModel.java:1135-1141
+ *                                 -> PartitionLoadState servlet/response/PartitionLoadState.java:56-151
  *   ccmi_compute_cluster_stats <- ClusterModel.getClusterStats(BalancingConstraint, OptimizationOptions)
  *                                 model/ClusterModel.java:137-139 -> ClusterModelStats.populate :84-102
  *   ccmi_action_log_*          <- the ordered relocateReplica/relocateLeadership calls a goal makes
@@ -596,6 +599,69 @@ typedef struct ccmi_disk_stats {
 ccmi_status ccmi_broker_stats(ccmi_session* s, ccmi_basic_stats* brokers /* [B] */,
                               ccmi_basic_stats* hosts /* [B] capacity, or NULL */, int32_t* num_hosts /* or NULL */,
                               ccmi_disk_stats* disks /* [num_disks], or NULL */);
+
+/* The parameters of a partition load request (PartitionLoadParameters). 64 bytes. */
+typedef struct ccmi_partition_load_query {
+  int32_t resource;         /* ccmi_resource: the sort key (PartitionLoadParameters.resource(), default DISK) */
+  int32_t want_max_load;    /* 0 / 1 */
+  int32_t want_avg_load;    /* 0 / 1 */
+  int32_t entries;          /* at most this many records (Integer.MAX_VALUE = all) */
+  int32_t partition_lower;  /* keep partition_number in [lower, upper], both inclusive */
+  int32_t partition_upper;  /* (Integer.MIN_VALUE / MAX_VALUE = no bound) */
+  int32_t reserved[4];      /* 0 (they bring the struct to 64 bytes) */
+  const uint8_t* topic_selected;  /* [T] or NULL = every topic: the caller evaluates its regex on the names */
+  const uint8_t* broker_selected;  /* [B] or NULL = every broker (brokerIds empty) */
+  const int32_t* tie_rank;         /* [P] or NULL = the partition index */
+} ccmi_partition_load_query;
+/* One PartitionLoadState record (PartitionLoadState.java:56-151). 80 bytes. */
+typedef struct ccmi_partition_load_record {
+  double util[4];        /* ccmi_resource order, all four under the query's max / avg flags */
+  int32_t partition;     /* partition index (desc order) */
+  int32_t num_replicas;
+  int32_t brokers[8];    /* current broker index of every replica in Partition._replicas order: [0] the leader,
+                            [1, num_replicas) the followers as Partition.followers() lists them; -1 beyond */
+  int32_t reserved[2];   /* 0 */
+} ccmi_partition_load_record;
+/* Additive at ABI v13 (the capability flag is the presence of the symbol). The partition load response of the session's
+ * current model (PartitionLoadRunnable.getResult, PartitionLoadRunnable.java:32-60): the selected partitions ordered by
+ * the utilization of q->resource on their current leader, computed and sorted on the device from the resident tables.
+ * Values: util[res] = partition.leader().load().expectedUtilizationFor(res, wantMaxLoad, wantAvgLoad) (Load.java:81-95):
+ * 0.0 for an empty load; else Math.max(0.0 + sum over the resource's metrics of (double) f(m), 0.0) with the metrics
+ * CPU: [CPU], DISK: [DISK], NW_IN: [LEADER_BYTES_IN, REPLICATION_BYTES_IN], NW_OUT: [LEADER_BYTES_OUT,
+ * REPLICATION_BYTES_OUT] and the float f(m) = MetricValues.max() with want_max_load, latest() (window 0) for DISK without
+ * want_avg_load, avg() = (float)(sum / W) otherwise; Math.max(x, 0.0) as Java evaluates it (-0.0 becomes 0.0). NaN loads
+ * are outside the contract.
+ * MetricValues.max() returns a cached _max (MetricValues.java:20, :165-171) that set() can leave stale (:39-45). For a
+ * replica that is currently the leader it nevertheless equals Math.max(Float.MIN_VALUE, max_i v[i]), which is what the
+ * call computes: every add / subtract recomputes _max from Float.MIN_VALUE over all windows (:86-92, :106-112, :126-131,
+ * :146-152); DISK, LEADER_BYTES_IN and REPLICATION_BYTES_IN of a replica are written once, by the add of
+ * Load.initializeMetricValues (Load.java:207-213), and never by set(); CPU, LEADER_BYTES_OUT and REPLICATION_BYTES_OUT of
+ * a leader were last written either by that same add (a leader since ingestion) or by makeLeader's Load.addLoad
+ * (Replica.java:306, Load.java:241-245), again an add — makeFollower's set() calls and clears happen only while the
+ * replica stops being the leader; and since _max >= Float.MIN_VALUE > 0 always, max() never takes its updateMax() branch
+ * (:166-170). So a leader whose windows are all zero (or negative) reports 2^-149 per metric in max mode, not 0, and a
+ * leader with an empty load 0.0. The response reads leaders only.
+ * MESSAGE_IN_RATE (the reference's msg_in column) is not one of the six metrics the model carries: it is left out.
+ * Order: partitionList.sort((o1, o2) -> Double.compare(o2, o1)) on util[q->resource], descending. Among exactly equal
+ * keys the reference's order is the iteration order of its HashMap<TopicPartition, Partition>, which the device does not
+ * hold: the caller passes it as tie_rank. Equal keys come in ascending tie_rank[p], then ascending partition index — a
+ * total order for any tie_rank contents (values may repeat and are compared as signed 32-bit integers).
+ * Selection (PartitionLoadRunnable.java:45-50, PartitionLoadState.shouldSkipPartition), before the entries cut: a
+ * partition is kept when topic_selected[topic] != 0 (or the array is NULL), its partition number lies in
+ * [partition_lower, partition_upper], and some current broker b of it has broker_selected[b] != 0 (or the array is
+ * NULL). *num_selected (optional) receives the number kept, *num_records = min(entries, kept), and records[0,
+ * *num_records) the first partitions of the order; records has room for min(entries, P) rows.
+ * The session is not changed. Valid on a fresh session, after any optimization and after ccmi_session_apply with nothing
+ * in between (the pending rows and loads are sent first). A sharded session answers locally. The launches count into
+ * stats_launches, stats_bytes and stats_kernel_ms of ccmi_perf_counters, as ccmi_broker_stats; no acceptance counter
+ * counts them.
+ * Errors, all before any launch: CCMI_E_INVALID for both flags set (the IllegalArgumentException of Load.java:82-84), a
+ * flag other than 0 / 1, resource outside [0, 4), entries < 0, a NULL s, q or num_records, or NULL records with
+ * entries > 0 and P > 0. partition_lower > partition_upper is CCMI_OK with 0 records. CCMI_E_DEVICE for a device failure;
+ * on error the outputs are unspecified. */
+ccmi_status ccmi_partition_load(ccmi_session* s, const ccmi_partition_load_query* q,
+                                ccmi_partition_load_record* records /* [min(entries, P)] */,
+                                int64_t* num_records, int64_t* num_selected /* optional */);
 
 int64_t ccmi_action_log_count(const ccmi_session* s);
 ccmi_status ccmi_action_log_copy(const ccmi_session* s, int64_t first, int64_t count, ccmi_action* out);
