@@ -815,6 +815,15 @@ ccmi_status ccmi_perf(const ccmi_session* s, ccmi_perf_counters* out) {
   });
 }
 
+ccmi_status ccmi_host_prefix_perf(const ccmi_session* s, ccmi_host_prefix_counters* out) {
+  return guarded([&] {
+    if (!s || !out) throw std::invalid_argument("null argument");
+    out->host_scans = s->device->perf.hostScans;
+    out->host_candidates = s->device->perf.hostCandidates;
+    return CCMI_OK;
+  });
+}
+
 void ccmi_perf_reset(ccmi_session* s) {
   if (s) {
     s->device->collectServerBusy();

@@ -68,6 +68,8 @@ struct DevicePerf {
   int64_t acceptLaunches = 0;   // K9 accept_actions launches (acceptBatch)
   int64_t acceptCells = 0;      // (action, goal) cells they answered
   double acceptKernelMs = 0;    // their HIP-event time (kernel timing on)
+  int64_t hostScans = 0;        // pair scans decided by the engine's host prefix (Engine::pairScan): nothing posted
+  int64_t hostCandidates = 0;   // candidates the host prefix evaluated, misses included
 };
 
 // K6 (kernels/intra.hip, intra.h): one intra-broker goal over every broker in one launch.

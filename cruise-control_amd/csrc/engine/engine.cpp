@@ -123,6 +123,14 @@ uint32_t needsOf(const DevGoal& g) {
 
 size_t idleTreePutsPerPoll() { return idleTreePuts(); }
 
+Engine::Engine(Model& m, Device* dev) : m(m), dev(dev) {
+  if (const char* v = std::getenv("CCMI_HOST_PREFIX")) {
+    const long long h = std::strtoll(v, nullptr, 10);
+    hostPrefix = h <= 0 ? 0 : (int)std::min<long long>(h, INT32_MAX);
+  }
+  if (const char* v = std::getenv("CCMI_HOST_PREFIX_GATE")) hostPrefixGate = v[0] != '0';
+}
+
 std::vector<int> GoalImpl::brokersToBalance(Engine& e) {
   std::vector<int> v(e.m.B);
   for (int b = 0; b < e.m.B; ++b) v[b] = b;
@@ -269,6 +277,7 @@ int64_t Engine::crossScan(GoalImpl& self, int action, const std::vector<int32_t>
   if (!found) key = scanRows(done, K - done, N);
   if (windows && key >= 0 && N > 2 * kProbeCols && !(self.probeHitRate > 0.9))  // learn whether the probe would win
     self.probeHitRate = 0.95 * self.probeHitRate + (key < kProbeCols ? 0.05 : 0.0);
+  prof().countDepth(DEPTH_CROSS, key);  // the key is the winner's position in row-major (first-sweep) order
   checkTerminal(key);
   if (count) {
     if (prog.exclLeadMove || prog.newOnly) candidates += exclLeadCount(prog, reps.data() + r0, K, cands, key);
@@ -298,6 +307,7 @@ int64_t Engine::crossScanSegs(GoalImpl& self, int action, const std::vector<Snap
   prog.filter = FILTER_NONE;
   dev->armGroupCombine();
   const int64_t key = combine(dev->scanSegs(prog, segs, cands.data(), N, 0, N));
+  prof().countDepth(DEPTH_CROSS, key);
   checkTerminal(key);
   candidates += key >= 0 ? key + 1 : K * N;
   return key;
@@ -451,16 +461,63 @@ int64_t Engine::combine(int64_t localKey) const {
   return k == INT64_MAX ? -1 : k;
 }
 
-int64_t Engine::pairScan(GoalImpl& self, const std::vector<int32_t>& pr, const std::vector<int32_t>& pb, int action,
-                         bool count) {
+// A server command stages at most kOverlayRows broker, replica and partition rows (Device::serveScan); past that the
+// scan costs a server stop, a prep + scan launch and a server restart. Host-decided scans post nothing, so their
+// actions' rows pile up: the host path is taken only while the pending rows (the model's dirty lists plus the device's
+// unsent lists) still fit one command after the action this scan may bring (at most 2 rows of each kind) and one more
+// as margin. Topic-count deltas (at most 4 per action) are bounded by what the same run of actions would carry.
+bool Engine::prefixBudget() const {
+  constexpr size_t kRowsAhead = 2 * 2, kDeltasAhead = 2 * 4;
+  auto fits = [](size_t pending) { return pending + kRowsAhead <= (size_t)kOverlayRows; };
+  return fits(m.bDirtyList.size() + dev->brows.size()) && fits(m.rDirtyList.size() + dev->rrows.size()) &&
+         fits(m.pDirtyList.size() + dev->prows.size()) && dev->tdeltas.size() + kDeltasAhead <= 2 * (size_t)kOverlayRows;
+}
+
+int64_t Engine::pairScan(GoalImpl& self, int site, const std::vector<int32_t>& pr, const std::vector<int32_t>& pb,
+                         int action, bool count) {
   if (pr.empty()) return -1;
-  PhaseScope ps(PH_DEV_SCAN);
-  m.flushToDevice();
   const int n = (int)pr.size();
-  const int p0 = (int)((int64_t)n * shard.rank / shard.count), p1 = (int)((int64_t)n * (shard.rank + 1) / shard.count);
   const DevProgram prog = program(self, action);
-  dev->armGroupCombine();
-  const int64_t key = combine(dev->scanPairs(prog, pr.data(), pb.data(), p0, p1));
+  // The host prefix: one shard, no combiner, no pair chains (those sessions scan exactly as before). Brokers that share
+  // hosts are left out too: an action there dirties every broker row of two hosts, which prefixBudget does not bound.
+  const bool prefixOn = hostPrefix > 0 && shard.count == 1 && !shard.fn && !pairChains && !m.sharedHosts;
+  PrefixGate& gate = self.prefixGate[site];
+  int64_t key = -1;
+  int h = 0;  // pairs [0, h) were rejected (or passed over as blocked) on the host
+  if (prefixOn && (!hostPrefixGate || gate.open())) {
+    if (prefixBudget()) {
+      PhaseScope ph(PH_HOST_PREFIX);
+      NsScope ns(64, "prefix.ns");
+      const HostView v{m, hostAllowedBySlot_, topicUpper, topicLower, brokerSetOf, replicaSetOf, minLeadOf, topicLeadLim};
+      h = std::min(hostPrefix, n);
+      int64_t evaluated = 0;
+      for (int q = 0; q < h && key < 0; ++q) {
+        if (blocked(prog, pr[q], pb[q])) continue;
+        ++evaluated;
+        if (moveCandidateAccepted(prog, v, pr[q], pb[q])) key = q;
+      }
+      dev->perf.hostCandidates += evaluated;
+      const bool decided = key >= 0 || h == n;
+      if (decided) dev->perf.hostScans++;
+      gate.feed(decided);
+      prof().count(65, "prefix.cands", evaluated);
+      prof().count(decided ? 66 : 67, decided ? "prefix.decided" : "prefix.missed", 1);
+    } else {
+      prof().count(68, "prefix.budget", 1);  // sent whole: the command carries the pending rows
+    }
+  }
+  if (key < 0 && h < n) {
+    PhaseScope ps(PH_DEV_SCAN);
+    m.flushToDevice();
+    const int p0 = (int)((int64_t)n * shard.rank / shard.count), p1 = (int)((int64_t)n * (shard.rank + 1) / shard.count);
+    dev->armGroupCombine();
+    key = combine(dev->scanPairs(prog, pr.data(), pb.data(), std::max(p0, h), p1));
+    if (prefixOn && h == 0) {  // a scan the device decided whole teaches the predictor what the prefix would have done
+      gate.served++;
+      gate.feed(key >= 0 ? key < hostPrefix : n <= hostPrefix);
+    }
+  }
+  prof().countDepth(DEPTH_PAIRS, key);
   checkTerminal(key);
   if (!count) return key;
   if (prog.exclLeadMove || prog.newOnly) {
@@ -798,6 +855,10 @@ bool Engine::optimizeGoalImpl(std::unique_ptr<GoalImpl>& g, ccmi_goal_result* re
   g->init(*this);
   g->dg.allowedSlot = newSlot;
   dev->setAllowed(g->dg.allowedSlot, g->allowed.data());
+  // the host view of the same table (pairScan's host prefix), built once per goal
+  hostAllowedBySlot_.assign(kMaxSlots, nullptr);
+  for (const auto& h : optimized) hostAllowedBySlot_[h->dg.allowedSlot] = &h->allowed;
+  hostAllowedBySlot_[g->dg.allowedSlot] = &g->allowed;
   if (opt.anyExclLead || opt.anyExclMove || m.numNew > 0 || exclOnDevice) {
     const std::vector<uint8_t> none(m.B, 0);
     std::vector<uint8_t> isNew(m.B, 0);
@@ -1814,7 +1875,7 @@ class ResourceDistribution : public GoalImpl {
             }
           }
         }
-        const int64_t key = e.pairScan(*this, pr, pb);
+        const int64_t key = e.pairScan(*this, PS_RES_OUT, pr, pb);
         if (key < 0) break;
         hitIdx = (size_t)pairOwner[key];
         dst = pb[key];
@@ -2172,7 +2233,7 @@ class ResourceDistribution : public GoalImpl {
           pb.push_back(b);
         }
       }
-      const int64_t key = rows.empty() ? -1 : e.pairScan(*this, pr, pb, DA_LEADERSHIP, false);
+      const int64_t key = rows.empty() ? -1 : e.pairScan(*this, PS_RES_IN, pr, pb, DA_LEADERSHIP, false);
       // reference-equivalent rows visited up to the accepted row (or everything left when nothing is accepted)
       int64_t visited = 0;
       Row hitRow{-1, 0, -1};

@@ -55,6 +55,33 @@ struct Constraint {  // BalancingConstraint
 
 class Engine;
 
+// Engine::pairScan's call sites: with the goal (a GoalImpl lives for one optimization) the key of the host-prefix
+// predictors. Every site scans with one action, so (goal, site) also separates the actions.
+enum PairSite {
+  PS_RES_OUT,  // ResourceDistributionGoal: leadership out of a broker
+  PS_RES_IN,   // ResourceDistributionGoal: leadership into a broker
+  PS_MIN_LEAD,  // MinTopicLeadersPerBrokerGoal: one leader to one broker
+  PS_CAPACITY,  // CapacityGoal: leadership out
+  PS_TLD_OUT, PS_TLD_IN,  // TopicLeaderReplicaDistributionGoal's two leadership loops
+  PS_LRD_OUT, PS_LRD_IN,  // LeaderReplicaDistributionGoal: leadership out / in
+  PS_LBI,  // LeaderBytesInDistributionGoal
+  kPairSites
+};
+
+// Host prefix of a pair scan (Engine::pairScan): the first pairs of a first-fit scan are evaluated on the host and a
+// winner among them saves the device round trip. One predictor per (goal, call site) decides whether the prefix is
+// tried: an EWMA of "the winner was within the prefix", fed by every scan of the site whichever side decided it. A site
+// starts on the device and turns to the host after kWarmup device-served scans with the rate above kThreshold; a
+// falling rate sends it back. Count-based, so two runs of one build make the same decisions.
+struct PrefixGate {
+  static constexpr int kWarmup = 16;
+  static constexpr double kThreshold = 0.5, kDecay = 0.95;
+  int served = 0;     // scans of the site the device decided whole
+  double rate = 0.0;  // recent share of scans won within the prefix
+  bool open() const { return served >= kWarmup && rate > kThreshold; }
+  void feed(bool withinPrefix) { rate = kDecay * rate + (withinPrefix ? 1.0 - kDecay : 0.0); }
+};
+
 // Puts of a speculative candidate-tree build per poll of an in-flight scan (Device::idleWork; CCMI_IDLE_TREE_PUTS,
 // 0 = off). Read per call.
 size_t idleTreePutsPerPoll();
@@ -80,6 +107,7 @@ class GoalImpl {
   ccmi_provision_response prov{};  // Goal.provisionResponse
   // crossScan's first-row probe (Engine::crossScan): recent share of scans won within the probe's columns
   double probeHitRate = 0.0;
+  PrefixGate prefixGate[kPairSites];  // pairScan's host-prefix predictors, one per call site
   // Goal.actionAcceptance throws IllegalStateException (KafkaAssignerDiskUsageDistributionGoal): as an optimized goal
   // it ends the optimization at the first candidate that reaches it (Engine::program stops the conjunction there)
   bool terminal = false;
@@ -95,7 +123,7 @@ class GoalImpl {
 
 class Engine {
  public:
-  Engine(Model& m, Device* dev) : m(m), dev(dev) {}
+  Engine(Model& m, Device* dev);
   Model& m;
   Device* dev;
   Options opt;
@@ -161,8 +189,16 @@ class Engine {
   bool exclOnDevice = false;  // the device's broker exclusion bits are set
   bool terminalOptimized() const;  // an optimized goal is `terminal`
   void checkTerminal(int64_t key) const;  // a candidate reached a terminal optimized goal: IllegalStateException
-  int64_t pairScan(GoalImpl& self, const std::vector<int32_t>& pr, const std::vector<int32_t>& pb,
+  // pairScan: the first accepted pair of (pr[q], pb[q]), or -1. The first hostPrefix pairs are decided on the host
+  // where the site's predictor expects the winner there (PrefixGate) and the pending rows leave room (prefixBudget).
+  int64_t pairScan(GoalImpl& self, int site, const std::vector<int32_t>& pr, const std::vector<int32_t>& pb,
                    int action = DA_LEADERSHIP, bool count = true);
+  // Host-prefix knobs, read when the engine is created: CCMI_HOST_PREFIX = pairs evaluated on the host before a pair
+  // scan is posted (0: none, every scan goes to the device as before), CCMI_HOST_PREFIX_GATE=0 = no predictor and no
+  // warm-up, always try the prefix (tests).
+  int hostPrefix = kDefaultHostPrefix;
+  bool hostPrefixGate = true;
+  static constexpr int kDefaultHostPrefix = 32;
   int64_t swapScan(GoalImpl& self, const std::vector<int32_t>& srcs, const std::vector<int32_t>& cbOff,
                    const std::vector<int32_t>& cbRep, const SwapLimit& lim = SwapLimit());
   void eligible(const std::vector<int32_t>& in, int action, std::vector<int32_t>& out) const;
@@ -214,6 +250,10 @@ class Engine {
   DevProgram program(const GoalImpl& self, int action) const;
   int64_t combine(int64_t localKey) const;
   void refreshAllowed(GoalImpl& g);
+  // the host view's allowed-broker table of the running optimization (optimizeGoalImpl): every optimized goal's and the
+  // optimizing goal's `allowed`, by slot
+  std::vector<const std::vector<uint8_t>*> hostAllowedBySlot_;
+  bool prefixBudget() const;  // the pending rows leave room for one more host-decided action
 };
 
 std::unique_ptr<GoalImpl> makeGoal(int kind);

@@ -578,7 +578,7 @@ class MinTopicLeaders : public GoalImpl {
       if (m.tlead(t, m.rBroker[leader]) <= mn) continue;
       if (cands.empty()) continue;  // maybeApplyBalancingAction over an empty eligible list
       pr[0] = leader;
-      if (e.pairScan(*this, pr, pb, DA_LEADERSHIP) < 0) continue;
+      if (e.pairScan(*this, PS_MIN_LEAD, pr, pb, DA_LEADERSHIP) < 0) continue;
       m.relocateLeadership(m.rPart[leader], m.rBroker[leader], b);
       if (++recv >= mn) return;
     }
@@ -881,7 +881,7 @@ class Capacity : public GoalImpl {
             owner.push_back((int)q);
           }
         }
-        const int64_t key = e.pairScan(*this, pr, pb);
+        const int64_t key = e.pairScan(*this, PS_CAPACITY, pr, pb);
         if (key < 0) break;
         const size_t k = (size_t)owner[key];
         const int dst = pb[key];
@@ -1548,7 +1548,7 @@ class TopicLeaderReplicaDistribution : public GoalImpl {
           leadOff.push_back((int32_t)pr.size());
         }
       }
-      const int64_t keyL = e.pairScan(*this, pr, pb, DA_LEADERSHIP, false);
+      const int64_t keyL = e.pairScan(*this, PS_TLD_OUT, pr, pb, DA_LEADERSHIP, false);
       size_t kL = end;  // the row owning pair keyL: the last row whose pairs start at or before it
       if (keyL >= 0) kL = i + (size_t)(std::upper_bound(leadOff.begin(), leadOff.end(), (int32_t)keyL) - leadOff.begin()) - 1;
       // replica-move candidates: ascending ids (the HashSet order when the row's set has no bucket collisions)
@@ -1704,7 +1704,7 @@ class TopicLeaderReplicaDistribution : public GoalImpl {
           if (!candMove.empty()) key = e.crossScan(*this, DA_MOVE, rows, 0, candMove);
         } else if (!candLead.empty()) {
           pbs.assign(rows.size(), dest);
-          key = e.pairScan(*this, rows, pbs, DA_LEADERSHIP, true);
+          key = e.pairScan(*this, PS_TLD_IN, rows, pbs, DA_LEADERSHIP, true);
         }
         if (key < 0) {
           i = j;
@@ -1858,7 +1858,7 @@ class LeaderReplicaDistribution : public GoalImpl {
     while (start < pr.size()) {
       spr.assign(pr.begin() + start, pr.end());
       spb.assign(pb.begin() + start, pb.end());
-      const int64_t key = e.pairScan(*this, spr, spb);
+      const int64_t key = e.pairScan(*this, PS_LRD_OUT, spr, spb);
       if (key < 0) break;
       const size_t at = start + (size_t)key;
       const int r = pr[at];
@@ -1901,7 +1901,7 @@ class LeaderReplicaDistribution : public GoalImpl {
     while (start < pr.size()) {
       spr.assign(pr.begin() + start, pr.end());
       spb.assign(pb.begin() + start, pb.end());
-      const int64_t key = e.pairScan(*this, spr, spb);
+      const int64_t key = e.pairScan(*this, PS_LRD_IN, spr, spb);
       if (key < 0) break;
       const size_t at = start + (size_t)key;
       m.relocateLeadership(m.rPart[pr[at]], m.rBroker[pr[at]], b);
@@ -2263,7 +2263,7 @@ class LeaderBytesIn : public GoalImpl {
           owner.push_back((int)q);
         }
       }
-      const int64_t key = e.pairScan(*this, pr, pb);
+      const int64_t key = e.pairScan(*this, PS_LBI, pr, pb);
       if (key < 0) break;
       const size_t k = (size_t)owner[key];
       const int dst = pb[key];

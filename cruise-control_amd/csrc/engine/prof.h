@@ -11,8 +11,23 @@ namespace ccmi {
 enum Phase {
   PH_RDG_OUT, PH_RDG_IN, PH_RES_OUT, PH_RES_IN, PH_SWAP, PH_DEV_SCAN, PH_DEV_STATS, PH_RELOCATE, PH_CAND_BUILD,
   PH_SORTED_INIT, PH_UPDATE, PH_PQ_INIT, PH_FLATTEN, PH_TREE_BUILD, PH_ORDER, PH_OTHER_GOALS, PH_SCAN_STAGE, PH_SCAN_WAIT,
-  PH_LEAD_OUT, PH_LEAD_IN, PH_REP_OUT, PH_REP_IN, PH_COUNT
+  PH_LEAD_OUT, PH_LEAD_IN, PH_REP_OUT, PH_REP_IN, PH_HOST_PREFIX, PH_COUNT
 };
+
+// Winner depth of a first-fit scan (candidates in front of the winner in scan order): the histogram buckets
+// 0, 1-3, 4-7, 8-15, 16-31, 32-63, 64-255, >=256 and "no winner" (depth < 0)
+constexpr int kDepthBuckets = 9;
+inline int depthBucket(int64_t depth) {
+  if (depth < 0) return 8;
+  if (depth == 0) return 0;
+  if (depth < 4) return 1;
+  if (depth < 8) return 2;
+  if (depth < 16) return 3;
+  if (depth < 32) return 4;
+  if (depth < 64) return 5;
+  return depth < 256 ? 6 : 7;
+}
+enum DepthOp { DEPTH_PAIRS, DEPTH_CROSS, DEPTH_OPS };
 
 struct PhaseProf {
   double ms[PH_COUNT] = {};
@@ -29,7 +44,7 @@ struct PhaseProf {
   }
   bool on = std::getenv("CCMI_PROFILE") != nullptr;
   // named event counters (diagnostics of the drivers' control flow)
-  static constexpr int kCounters = 64;
+  static constexpr int kCounters = 72;
   const char* counterName[kCounters] = {};
   int64_t counter[kCounters] = {};
   void count(int i, const char* name, int64_t d = 1) {
@@ -37,12 +52,21 @@ struct PhaseProf {
     counterName[i] = name;
     counter[i] += d;
   }
+  // winner depths of the drivers' scans: per op, and per op and driver phase (row PH_COUNT: outside every driver)
+  int64_t depth[DEPTH_OPS][kDepthBuckets] = {};
+  int64_t depthByPhase[PH_COUNT + 1][DEPTH_OPS][kDepthBuckets] = {};
+  void countDepth(int op, int64_t d) {
+    if (!on) return;
+    const int k = depthBucket(d);
+    depth[op][k]++;
+    depthByPhase[driver >= 0 ? driver : PH_COUNT][op][k]++;
+  }
   void print(const char* tag) const {
     static const char* names[PH_COUNT] = {"rdg.moveOut", "rdg.moveIn", "res.moveOut", "res.moveIn", "res.swap",
                                           "device.scan", "device.stats", "relocate", "cand.build", "sorted.init",
                                           "goal.update", "pq.init", "flatten", "tree.build", "order.repair",
                                           "other.goals", "scan.stage", "scan.wait",
-                                          "lrd.leadOut", "lrd.leadIn", "lrd.repOut", "lrd.repIn"};
+                                          "lrd.leadOut", "lrd.leadIn", "lrd.repOut", "lrd.repIn", "host.prefix"};
     if (!on) return;
     std::fprintf(stderr, "[ccmi profile %s]\n", tag);
     for (int i = 0; i < PH_COUNT; ++i)
@@ -56,6 +80,21 @@ struct PhaseProf {
       }
     for (int i = 0; i < kCounters; ++i)
       if (counterName[i]) std::fprintf(stderr, "  #%-28s %12lld\n", counterName[i], (long long)counter[i]);
+    static const char* ops[DEPTH_OPS] = {"pairs", "cross"};
+    auto row = [](const char* what, const char* where, const int64_t* h) {
+      int64_t all = 0;
+      for (int k = 0; k < kDepthBuckets; ++k) all += h[k];
+      if (!all) return;
+      std::fprintf(stderr, "  depth %-5s %-12s", what, where);
+      for (int k = 0; k < kDepthBuckets; ++k) std::fprintf(stderr, " %9lld", (long long)h[k]);
+      std::fprintf(stderr, "\n");
+    };
+    std::fprintf(stderr, "  depth %-5s %-12s %9s %9s %9s %9s %9s %9s %9s %9s %9s\n", "op", "phase", "0", "1-3", "4-7", "8-15",
+                 "16-31", "32-63", "64-255", ">=256", "none");
+    for (int o = 0; o < DEPTH_OPS; ++o) {
+      row(ops[o], "all", depth[o]);
+      for (int i = 0; i <= PH_COUNT; ++i) row(ops[o], i < PH_COUNT ? names[i] : "(no driver)", depthByPhase[i][o]);
+    }
   }
 };
 

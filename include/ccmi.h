@@ -766,6 +766,15 @@ ccmi_status ccmi_perf(const ccmi_session* s, ccmi_perf_counters* out);
 void ccmi_perf_reset(ccmi_session* s);
 /* Record HIP events around every scan/stats kernel (adds a little host overhead; off by default). */
 void ccmi_set_kernel_timing(ccmi_session* s, int32_t enabled);
+/* Host-prefix counters (additive at ABI v13: the capability flag is the presence of the symbol, ccmi_perf_counters
+ * keeps its layout). A pair scan's first CCMI_HOST_PREFIX pairs are evaluated on the host where that is expected to
+ * decide the scan; such a scan posts nothing to the device, so scan_required, server_required,
+ * server_scans and host_syncs of ccmi_perf_counters keep counting device work only. ccmi_perf_reset clears these too. */
+typedef struct ccmi_host_prefix_counters {
+  int64_t host_scans;      /* pair scans decided on the host: a winner within the prefix, or a list no longer than it */
+  int64_t host_candidates; /* candidates evaluated on the host, those of prefixes that missed included */
+} ccmi_host_prefix_counters;
+ccmi_status ccmi_host_prefix_perf(const ccmi_session* s, ccmi_host_prefix_counters* out);
 
 #ifdef __cplusplus
 }
