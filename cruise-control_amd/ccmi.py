@@ -193,6 +193,10 @@ class HostPrefixPerfStruct(C.Structure):  # ccmi_host_prefix_counters
     _fields_ = [("host_scans", C.c_int64), ("host_candidates", C.c_int64)]
 
 
+class HostCrossPerfStruct(C.Structure):  # ccmi_host_cross_counters
+    _fields_ = [("host_cross_scans", C.c_int64), ("host_cross_candidates", C.c_int64)]
+
+
 class BasicStatsStruct(C.Structure):  # ccmi_basic_stats: one broker's or one host's BasicStats, 128 bytes
     _fields_ = [("disk_mb", C.c_double), ("disk_pct", C.c_double), ("cpu_pct", C.c_double),
                 ("leader_nw_in_rate", C.c_double), ("follower_nw_in_rate", C.c_double), ("nw_out_rate", C.c_double),
@@ -257,7 +261,7 @@ EXPORTED_SYMBOLS = (
     "ccmi_session_apply", "ccmi_last_failure_provision",
     "ccmi_compute_cluster_stats", "ccmi_broker_stats", "ccmi_partition_load", "ccmi_action_log_count", "ccmi_action_log_copy", "ccmi_replica_distribution",
     "ccmi_leader_distribution", "ccmi_replica_disks", "ccmi_proposal_count", "ccmi_proposals",
-    "ccmi_proposal_disks", "ccmi_perf", "ccmi_perf_reset", "ccmi_host_prefix_perf",
+    "ccmi_proposal_disks", "ccmi_perf", "ccmi_perf_reset", "ccmi_host_prefix_perf", "ccmi_host_cross_perf",
     "ccmi_set_kernel_timing", "ccmi_session_set_shard", "ccmi_rccl_unique_id", "ccmi_session_attach_rccl",
     "ccmi_session_attach_shm", "ccmi_session_attach_shm_job", "ccmi_shard_group_create", "ccmi_shard_group_destroy", "ccmi_session_attach_group",
     "ccmi_topic_broker_set",
@@ -316,6 +320,9 @@ class Library:
         self.has_host_prefix_perf = hasattr(L, "ccmi_host_prefix_perf")
         if self.has_host_prefix_perf:
             L.ccmi_host_prefix_perf.argtypes = [C.c_void_p, C.POINTER(HostPrefixPerfStruct)]
+        self.has_host_cross_perf = hasattr(L, "ccmi_host_cross_perf")
+        if self.has_host_cross_perf:
+            L.ccmi_host_cross_perf.argtypes = [C.c_void_p, C.POINTER(HostCrossPerfStruct)]
         self.has_partition_load = hasattr(L, "ccmi_partition_load")
         if self.has_partition_load:
             L.ccmi_partition_load.argtypes = [C.c_void_p, C.POINTER(PartitionLoadQueryStruct), C.c_void_p,
@@ -1588,6 +1595,10 @@ class ClusterModel:
         if self.lib.has_host_prefix_perf:
             self.lib.check(self.lib.lib.ccmi_host_prefix_perf(self.handle, C.byref(h)))
         p.host_scans, p.host_candidates = h.host_scans, h.host_candidates
+        x = HostCrossPerfStruct()
+        if self.lib.has_host_cross_perf:
+            self.lib.check(self.lib.lib.ccmi_host_cross_perf(self.handle, C.byref(x)))
+        p.host_cross_scans, p.host_cross_candidates = x.host_cross_scans, x.host_cross_candidates
         return p
 
     def reset_perf(self) -> None:

@@ -824,6 +824,15 @@ ccmi_status ccmi_host_prefix_perf(const ccmi_session* s, ccmi_host_prefix_counte
   });
 }
 
+ccmi_status ccmi_host_cross_perf(const ccmi_session* s, ccmi_host_cross_counters* out) {
+  return guarded([&] {
+    if (!s || !out) throw std::invalid_argument("null argument");
+    out->host_cross_scans = s->device->perf.hostCrossScans;
+    out->host_cross_candidates = s->device->perf.hostCrossCandidates;
+    return CCMI_OK;
+  });
+}
+
 void ccmi_perf_reset(ccmi_session* s) {
   if (s) {
     s->device->collectServerBusy();

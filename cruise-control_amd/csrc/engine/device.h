@@ -70,6 +70,8 @@ struct DevicePerf {
   double acceptKernelMs = 0;    // their HIP-event time (kernel timing on)
   int64_t hostScans = 0;        // pair scans decided by the engine's host prefix (Engine::pairScan): nothing posted
   int64_t hostCandidates = 0;   // candidates the host prefix evaluated, misses included
+  int64_t hostCrossScans = 0;       // cross scans decided by the host prefix (Engine::crossScan / crossScanSegs)
+  int64_t hostCrossCandidates = 0;  // candidates the cross host prefix evaluated, misses included
 };
 
 // K6 (kernels/intra.hip, intra.h): one intra-broker goal over every broker in one launch.

@@ -128,6 +128,10 @@ Engine::Engine(Model& m, Device* dev) : m(m), dev(dev) {
     const long long h = std::strtoll(v, nullptr, 10);
     hostPrefix = h <= 0 ? 0 : (int)std::min<long long>(h, INT32_MAX);
   }
+  if (const char* v = std::getenv("CCMI_HOST_PREFIX_CROSS")) {
+    const long long h = std::strtoll(v, nullptr, 10);
+    hostPrefixCross = h <= 0 ? 0 : (int)std::min<long long>(h, INT32_MAX);
+  }
   if (const char* v = std::getenv("CCMI_HOST_PREFIX_GATE")) hostPrefixGate = v[0] != '0';
 }
 
@@ -239,44 +243,122 @@ int64_t Engine::exclLeadCount(const DevProgram& prog, const int32_t* reps, int K
   return c;
 }
 
-int64_t Engine::crossScan(GoalImpl& self, int action, const std::vector<int32_t>& reps, size_t r0,
+// Cross scans take the host prefix under pairScan's rules (one shard, no combiner, no pair chains, no shared hosts);
+// rack-filtered scans (FILTER_RACK_AWARE) always go to the device.
+bool Engine::crossPrefixOn(const DevProgram& prog) const {
+  return hostPrefixCross > 0 && prog.filter == FILTER_NONE && shard.count == 1 && !shard.fn && !pairChains && !m.sharedHosts;
+}
+
+namespace {
+constexpr int kRowWindow = 32, kProbeCols = 1024;  // crossScan's row window and first-row probe
+bool scanWindows() {
+  static const bool windows = !std::getenv("CCMI_SCAN_NO_WINDOWS");  // A/B diagnostics: one scan over every row
+  return windows;
+}
+}  // namespace
+
+// The first min(hostPrefixCross, K * N) candidates of the scan in the device's key order (row-major: key = k * N + j),
+// with the conjunction the kernels apply to the same (row, column): in the list (Engine::blocked) and accepted.
+bool Engine::crossHostPrefix(PrefixGate& gate, const DevProgram& prog, const int32_t* rows, int64_t K,
+                             const std::vector<int32_t>& cands, int64_t& key, bool& tried) {
+  key = -1;
+  tried = false;
+  if (hostPrefixGate && !gate.open()) return false;
+  if (!prefixBudget()) {
+    prof().count(73, "xprefix.budget", 1);  // sent whole: the command carries the pending rows
+    return false;
+  }
+  tried = true;
+  PhaseScope ph(PH_HOST_PREFIX);
+  NsScope ns(69, "xprefix.ns");
+  const HostView v{m, hostAllowedBySlot_, topicUpper, topicLower, brokerSetOf, replicaSetOf, minLeadOf, topicLeadLim};
+  const int N = (int)cands.size();
+  const int64_t h = std::min<int64_t>(hostPrefixCross, K * N);
+  const bool filters = prog.exclLeadMove || prog.newOnly;
+  int64_t evaluated = 0;
+  int k = 0, j = 0;
+  for (int64_t q = 0; q < h; ++q) {
+    const int r = rows[k], b = cands[j];
+    if (!(filters && blocked(prog, r, b))) {
+      ++evaluated;
+      if (moveCandidateAccepted(prog, v, r, b)) {
+        key = q;
+        break;
+      }
+    }
+    if (++j == N) {
+      j = 0;
+      ++k;
+    }
+  }
+  const bool decided = key >= 0 || h == K * N;
+  dev->perf.hostCrossCandidates += evaluated;
+  if (decided) dev->perf.hostCrossScans++;
+  gate.feed(decided);
+  prof().count(70, "xprefix.cands", evaluated);
+  prof().count(decided ? 71 : 72, decided ? "xprefix.decided" : "xprefix.missed", 1);
+  return decided;
+}
+
+void Engine::crossLearnGate(PrefixGate& gate, int64_t key, int64_t K, int N) const {
+  gate.served++;
+  gate.feed(key >= 0 ? key < hostPrefixCross : K * N <= hostPrefixCross);
+}
+
+// crossScan's probe bookkeeping as a function of the scan's key: the probe (run while the rate is above 0.9) wins
+// exactly when the key lies within the first row's first kProbeCols columns, and a scan without a probe learns whether
+// one would have won. A host-decided scan makes the same updates a device-decided scan with its key makes.
+void Engine::crossLearnProbe(GoalImpl& self, int64_t key, int N) const {
+  if (!scanWindows() || N <= 2 * kProbeCols) return;
+  if (self.probeHitRate > 0.9) self.probeHitRate = 0.95 * self.probeHitRate + (key >= 0 && key < kProbeCols ? 0.05 : 0.0);
+  if (key >= 0 && !(self.probeHitRate > 0.9)) self.probeHitRate = 0.95 * self.probeHitRate + (key < kProbeCols ? 0.05 : 0.0);
+}
+
+int64_t Engine::crossScan(GoalImpl& self, int site, int action, const std::vector<int32_t>& reps, size_t r0,
                           const std::vector<int32_t>& cands, int filter, bool count, size_t r1) {
   const size_t end = r1 == (size_t)-1 ? reps.size() : std::min(r1, reps.size());
   const int K = (int)(end - r0), N = (int)cands.size();
   if (K <= 0) return -1;
   if (N == 0) return -1;  // every replica visits an empty eligible list
-  PhaseScope ps(PH_DEV_SCAN);
-  m.flushToDevice();
   DevProgram prog = program(self, action);
   prog.filter = filter;
-  // Rows are scanned in windows: a first-fit winner in the first rows is the same winner whatever follows them,
-  // so a scan that is usually won early does not send (nor evaluate) every row. The first window can also be a
-  // probe of the first row's first kProbeCols columns, used while this goal's scans mostly end there.
-  constexpr int kRowWindow = 32, kProbeCols = 1024;
-  auto scanRows = [&](int k0, int nk, int cEnd) -> int64_t {  // rows [k0, k0 + nk) x columns [0, cEnd) of N
-    const int s0 = (int)((int64_t)cEnd * shard.rank / shard.count), s1 = (int)((int64_t)cEnd * (shard.rank + 1) / shard.count);
-    dev->armGroupCombine();
-    const int64_t k = combine(dev->scanCross(prog, reps.data() + r0 + k0, nk, cands.data(), N, s0, s1));
-    return k < 0 ? -1 : k + (int64_t)k0 * N;
-  };
-  static const bool windows = !std::getenv("CCMI_SCAN_NO_WINDOWS");  // A/B diagnostics: one scan over every row
+  const bool prefixOn = crossPrefixOn(prog);
+  PrefixGate& gate = self.crossGate[site];
   int64_t key = -1;
-  int done = 0;  // rows fully scanned without a winner
-  bool found = !windows;
-  if (!windows) key = scanRows(0, K, N);
-  if (!found && N > 2 * kProbeCols && self.probeHitRate > 0.9) {
-    key = scanRows(0, 1, kProbeCols);
-    found = key >= 0;
-    self.probeHitRate = 0.95 * self.probeHitRate + (found ? 0.05 : 0.0);
+  bool tried = false;
+  if (prefixOn && crossHostPrefix(gate, prog, reps.data() + r0, K, cands, key, tried)) {
+    crossLearnProbe(self, key, N);  // nothing was flushed or posted
+  } else {
+    PhaseScope ps(PH_DEV_SCAN);
+    m.flushToDevice();
+    // Rows are scanned in windows: a first-fit winner in the first rows is the same winner whatever follows them,
+    // so a scan that is usually won early does not send (nor evaluate) every row. The first window can also be a
+    // probe of the first row's first kProbeCols columns, used while this goal's scans mostly end there.
+    auto scanRows = [&](int k0, int nk, int cEnd) -> int64_t {  // rows [k0, k0 + nk) x columns [0, cEnd) of N
+      const int s0 = (int)((int64_t)cEnd * shard.rank / shard.count), s1 = (int)((int64_t)cEnd * (shard.rank + 1) / shard.count);
+      dev->armGroupCombine();
+      const int64_t k = combine(dev->scanCross(prog, reps.data() + r0 + k0, nk, cands.data(), N, s0, s1));
+      return k < 0 ? -1 : k + (int64_t)k0 * N;
+    };
+    const bool windows = scanWindows();
+    int done = 0;  // rows fully scanned without a winner
+    bool found = !windows;
+    if (!windows) key = scanRows(0, K, N);
+    if (!found && N > 2 * kProbeCols && self.probeHitRate > 0.9) {
+      key = scanRows(0, 1, kProbeCols);
+      found = key >= 0;
+      self.probeHitRate = 0.95 * self.probeHitRate + (found ? 0.05 : 0.0);
+    }
+    if (!found && K > 2 * kRowWindow) {
+      key = scanRows(0, kRowWindow, N);
+      found = key >= 0;
+      done = kRowWindow;
+    }
+    if (!found) key = scanRows(done, K - done, N);
+    if (windows && key >= 0 && N > 2 * kProbeCols && !(self.probeHitRate > 0.9))  // learn whether the probe would win
+      self.probeHitRate = 0.95 * self.probeHitRate + (key < kProbeCols ? 0.05 : 0.0);
+    if (prefixOn && !tried) crossLearnGate(gate, key, K, N);  // decided whole on the device: what the prefix would have done
   }
-  if (!found && K > 2 * kRowWindow) {
-    key = scanRows(0, kRowWindow, N);
-    found = key >= 0;
-    done = kRowWindow;
-  }
-  if (!found) key = scanRows(done, K - done, N);
-  if (windows && key >= 0 && N > 2 * kProbeCols && !(self.probeHitRate > 0.9))  // learn whether the probe would win
-    self.probeHitRate = 0.95 * self.probeHitRate + (key < kProbeCols ? 0.05 : 0.0);
   prof().countDepth(DEPTH_CROSS, key);  // the key is the winner's position in row-major (first-sweep) order
   checkTerminal(key);
   if (count) {
@@ -286,7 +368,7 @@ int64_t Engine::crossScan(GoalImpl& self, int action, const std::vector<int32_t>
   return key;
 }
 
-int64_t Engine::crossScanSegs(GoalImpl& self, int action, const std::vector<SnapSeg>& segs,
+int64_t Engine::crossScanSegs(GoalImpl& self, int site, int action, const std::vector<SnapSeg>& segs,
                               const std::vector<int32_t>& cands) {
   DevProgram prog = program(self, action);
   if (!dev->segsUsable() || shard.count > 1 || prog.exclLeadMove || prog.newOnly) {
@@ -296,17 +378,34 @@ int64_t Engine::crossScanSegs(GoalImpl& self, int action, const std::vector<Snap
       for (const SnapSeg& sg : segs)
         if (sg.v->size() > sg.skip) flat.insert(flat.end(), sg.v->begin() + sg.skip, sg.v->end());
     }
-    return crossScan(self, action, flat, 0, cands);
+    return crossScan(self, site, action, flat, 0, cands);
   }
   int64_t K = 0;
   for (const SnapSeg& sg : segs) K += sg.v->size() > sg.skip ? (int64_t)(sg.v->size() - sg.skip) : 0;
   const int N = (int)cands.size();
   if (K <= 0 || N == 0) return -1;
-  PhaseScope ps(PH_DEV_SCAN);
-  m.flushToDevice();
   prog.filter = FILTER_NONE;
-  dev->armGroupCombine();
-  const int64_t key = combine(dev->scanSegs(prog, segs, cands.data(), N, 0, N));
+  const bool prefixOn = crossPrefixOn(prog);
+  PrefixGate& gate = self.crossGate[site];
+  int64_t key = -1;
+  bool tried = false, decided = false;
+  if (prefixOn && (!hostPrefixGate || gate.open())) {
+    // the prefix's rows: the segments' rows after each segment's skip, in order
+    const size_t want = (size_t)std::min<int64_t>(K, ((int64_t)hostPrefixCross + N - 1) / N);
+    segPrefixRows_.clear();
+    for (const SnapSeg& sg : segs) {
+      for (size_t i = sg.skip; i < sg.v->size() && segPrefixRows_.size() < want; ++i) segPrefixRows_.push_back((*sg.v)[i]);
+      if (segPrefixRows_.size() >= want) break;
+    }
+    decided = crossHostPrefix(gate, prog, segPrefixRows_.data(), K, cands, key, tried);
+  }
+  if (!decided) {
+    PhaseScope ps(PH_DEV_SCAN);
+    m.flushToDevice();
+    dev->armGroupCombine();
+    key = combine(dev->scanSegs(prog, segs, cands.data(), N, 0, N));
+    if (prefixOn && !tried) crossLearnGate(gate, key, K, N);
+  }
   prof().countDepth(DEPTH_CROSS, key);
   checkTerminal(key);
   candidates += key >= 0 ? key + 1 : K * N;
@@ -1098,7 +1197,7 @@ class ReplicaDistribution : public GoalImpl {
         seq = &inorder;
       }
       const std::vector<int32_t>& cl = e.eligibleView(*seq, DA_MOVE, cands);
-      const int64_t key = e.crossScan(*this, DA_MOVE, batch, 0, cl);
+      const int64_t key = e.crossScan(*this, XS_OUT, DA_MOVE, batch, 0, cl);
       if (key < 0) {
         if (runOffline) wasUnable = true;
         i = e2;
@@ -1163,7 +1262,7 @@ class ReplicaDistribution : public GoalImpl {
         segs.push_back({s, m.sorted(s, kName), 0});
         flat.insert(flat.end(), segs.back().list.begin(), segs.back().list.end());
       }
-      const int64_t key = e.crossScan(*this, DA_MOVE, flat, 0, cands);
+      const int64_t key = e.crossScan(*this, XS_IN, DA_MOVE, flat, 0, cands);
       if (key < 0) {
         target = std::min<size_t>(target * kBatchGrowth, kMaxBatchRows);
         continue;  // all segments exhausted; sources are not re-enqueued
@@ -1823,7 +1922,7 @@ class ResourceDistribution : public GoalImpl {
           }
           cl = &e.eligibleView(*seq, DA_MOVE, cands);
         }
-        const int64_t key = e.crossScan(*this, DA_MOVE, list, i, *cl);
+        const int64_t key = e.crossScan(*this, XS_OUT, DA_MOVE, list, i, *cl);
         if (key < 0) break;
         const int N = (int)cl->size();
         hitIdx = i + (size_t)(key / N);
@@ -2026,7 +2125,7 @@ class ResourceDistribution : public GoalImpl {
         (void)m.snapshotInShared(snapTab, cb, spec);
         return true;
       };
-      const int64_t key = cands.empty() ? -1 : e.crossScanSegs(*this, action, segs, cands);
+      const int64_t key = cands.empty() ? -1 : e.crossScanSegs(*this, XS_SEGS, action, segs, cands);
       e.dev->idleWork = nullptr;  // (idleScope also clears it on a throw)
       if (key < 0) {
         target = std::min<size_t>(target * kBatchGrowth, kMaxBatchRows);

@@ -82,6 +82,16 @@ struct PrefixGate {
   void feed(bool withinPrefix) { rate = kDecay * rate + (withinPrefix ? 1.0 - kDecay : 0.0); }
 };
 
+// Engine::crossScan / crossScanSegs call sites, the key of the cross host prefix's predictors. A predictor belongs to
+// one goal (GoalImpl::crossGate), so a site only has to be distinct among the scans of one goal class.
+enum CrossSite {
+  XS_OUT,   // replicas out of the broker being balanced
+  XS_OUT2,  // a goal's second move-out loop (MinTopicLeaders' single leader, TopicLeaderReplicaDistribution's own list)
+  XS_IN,    // replicas into the broker being balanced
+  XS_SEGS,  // crossScanSegs (move-in over snapshot segments)
+  kCrossSites
+};
+
 // Puts of a speculative candidate-tree build per poll of an in-flight scan (Device::idleWork; CCMI_IDLE_TREE_PUTS,
 // 0 = off). Read per call.
 size_t idleTreePutsPerPoll();
@@ -108,6 +118,7 @@ class GoalImpl {
   // crossScan's first-row probe (Engine::crossScan): recent share of scans won within the probe's columns
   double probeHitRate = 0.0;
   PrefixGate prefixGate[kPairSites];  // pairScan's host-prefix predictors, one per call site
+  PrefixGate crossGate[kCrossSites];  // the cross scans' host-prefix predictors, one per call site
   // Goal.actionAcceptance throws IllegalStateException (KafkaAssignerDiskUsageDistributionGoal): as an optimized goal
   // it ends the optimization at the first candidate that reaches it (Engine::program stops the conjunction there)
   bool terminal = false;
@@ -160,12 +171,13 @@ class Engine {
 
   // device scans: return winning index or -1; add reference-equivalent candidate counts
   //   crossScan: rows reps[r0, r1) x cands, key = k * N + j; `count` adds the reference-equivalent candidates
-  //   (callers with candidate filters or early exits count themselves)
-  int64_t crossScan(GoalImpl& self, int action, const std::vector<int32_t>& reps, size_t r0,
+  //   (callers with candidate filters or early exits count themselves). The first hostPrefixCross candidates in key
+  //   order are decided on the host under pairScan's rules (crossHostPrefix); `site` keys the predictor.
+  int64_t crossScan(GoalImpl& self, int site, int action, const std::vector<int32_t>& reps, size_t r0,
                     const std::vector<int32_t>& cands, int filter = FILTER_NONE, bool count = true,
                     size_t r1 = (size_t)-1);
   // crossScan over the concatenation of snapshot segments (Device::scanSegs: the rows stay device-resident)
-  int64_t crossScanSegs(GoalImpl& self, int action, const std::vector<SnapSeg>& segs,
+  int64_t crossScanSegs(GoalImpl& self, int site, int action, const std::vector<SnapSeg>& segs,
                         const std::vector<int32_t>& cands);
   // Queue scans (Device::scanQueue): the rows of every broker of [head (if >= 0)] ++ tail[0, nTail) (poll order; entry 0
   // from row skip0) x cands in
@@ -199,6 +211,10 @@ class Engine {
   int hostPrefix = kDefaultHostPrefix;
   bool hostPrefixGate = true;
   static constexpr int kDefaultHostPrefix = 32;
+  // CCMI_HOST_PREFIX_CROSS = candidates (row-major key order) evaluated on the host before a cross scan is posted (0:
+  // none); CCMI_HOST_PREFIX keeps meaning pair scans only. The gate knob covers both.
+  int hostPrefixCross = kDefaultHostPrefixCross;
+  static constexpr int kDefaultHostPrefixCross = 64;
   int64_t swapScan(GoalImpl& self, const std::vector<int32_t>& srcs, const std::vector<int32_t>& cbOff,
                    const std::vector<int32_t>& cbRep, const SwapLimit& lim = SwapLimit());
   void eligible(const std::vector<int32_t>& in, int action, std::vector<int32_t>& out) const;
@@ -254,6 +270,16 @@ class Engine {
   // optimizing goal's `allowed`, by slot
   std::vector<const std::vector<uint8_t>*> hostAllowedBySlot_;
   bool prefixBudget() const;  // the pending rows leave room for one more host-decided action
+  // The host prefix of a cross scan of K rows x cands whose first rows are rows[0, nRows) (nRows covers the prefix):
+  // true when the host decided the scan (key: the winner, or -1 for a list no longer than the prefix that accepts
+  // nothing); false when the scan goes to the device whole (`tried` tells a miss from a scan not attempted).
+  bool crossHostPrefix(PrefixGate& gate, const DevProgram& prog, const int32_t* rows, int64_t K,
+                       const std::vector<int32_t>& cands, int64_t& key, bool& tried);
+  bool crossPrefixOn(const DevProgram& prog) const;
+  std::vector<int32_t> segPrefixRows_;  // crossScanSegs: the prefix's rows gathered from the segments (scratch)
+  // what a device-decided cross scan with this key teaches the site's predictor and the goal's probe rate
+  void crossLearnGate(PrefixGate& gate, int64_t key, int64_t K, int N) const;
+  void crossLearnProbe(GoalImpl& self, int64_t key, int N) const;
 };
 
 std::unique_ptr<GoalImpl> makeGoal(int kind);

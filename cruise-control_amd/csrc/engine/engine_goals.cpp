@@ -264,7 +264,7 @@ class RackAware : public GoalImpl {
     for (int r : list) {
       if (m.alive(b) && !m.curOffline(r) && keep(m, r)) continue;
       one[0] = r;
-      const int64_t key = e.crossScan(*this, DA_MOVE, one, 0, cands, FILTER_RACK_AWARE, false);
+      const int64_t key = e.crossScan(*this, XS_OUT, DA_MOVE, one, 0, cands, FILTER_RACK_AWARE, false);
       e.candidates += eligibleCount(e, r, cands, key >= 0 ? (size_t)key + 1 : cands.size());
       if (key < 0)
         throw OptimizationFailure("[" + name + "] Cannot move replica of partition " + std::to_string(m.rPart[r]) +
@@ -431,7 +431,7 @@ class RackAwareDist : public GoalImpl {
       eligibleFor(m, r, tree);
       e.eligible(tree, DA_MOVE, cands);
       one[0] = r;
-      const int64_t key = e.crossScan(*this, DA_MOVE, one, 0, cands);
+      const int64_t key = e.crossScan(*this, XS_OUT, DA_MOVE, one, 0, cands);
       if (key >= 0) m.relocateReplica(m.rPart[r], b, cands[key]);  // else: logged and skipped (:166)
     }
   }
@@ -599,7 +599,7 @@ class MinTopicLeaders : public GoalImpl {
       for (int r : m.sorted(giver, id))
         if (m.rLeader[r] && m.pTopic[m.rPart[r]] == t) leaders.push_back(r);
       int giverCount = (int)leaders.size();
-      const int64_t key = e.crossScan(*this, DA_MOVE, leaders, 0, cands);
+      const int64_t key = e.crossScan(*this, XS_OUT, DA_MOVE, leaders, 0, cands);
       if (key < 0) continue;
       const int r = leaders[key / (int64_t)cands.size()];
       m.relocateReplica(m.rPart[r], giver, b);
@@ -632,7 +632,7 @@ class MinTopicLeaders : public GoalImpl {
     copy.order(offline);
     for (int r : offline) {
       one[0] = r;
-      const int64_t key = e.crossScan(*this, DA_MOVE, one, 0, cands);
+      const int64_t key = e.crossScan(*this, XS_OUT2, DA_MOVE, one, 0, cands);
       if (key < 0)
         throw OptimizationFailure("[" + name + "] Cannot remove offline replica from broker " + std::to_string(m.bId[b]),
                                   underBrokers(1));
@@ -724,7 +724,7 @@ class ReplicaCapacity : public GoalImpl {
         built = true;
       }
       e.eligible(order, DA_MOVE, cands);
-      const int64_t key = e.crossScan(*this, DA_MOVE, list, i, cands, FILTER_NONE, true, end);
+      const int64_t key = e.crossScan(*this, XS_OUT, DA_MOVE, list, i, cands, FILTER_NONE, true, end);
       if (key < 0) {
         for (size_t q = i; q < end; ++q) fail(list[q]);
         i = end;
@@ -912,7 +912,7 @@ class Capacity : public GoalImpl {
       const std::vector<int32_t> list = m.sorted(b, sortId(kind, true, false));
       size_t i = 0;
       while (i < list.size()) {
-        const int64_t key = e.crossScan(*this, DA_MOVE, list, i, cands);
+        const int64_t key = e.crossScan(*this, XS_OUT, DA_MOVE, list, i, cands);
         if (key < 0) break;
         const size_t k = i + (size_t)(key / (int64_t)cands.size());
         m.relocateReplica(m.rPart[list[k]], b, cands[key % (int64_t)cands.size()]);
@@ -1010,7 +1010,7 @@ class PotentialNwOut : public GoalImpl {
       });
       e.eligible(sortedC, DA_MOVE, cands);
       for (size_t j = 0; j < cands.size(); ++j) pos[cands[j]] = (int)j;
-      const int64_t key = e.crossScan(*this, DA_MOVE, list, i, cands, FILTER_NONE, false);
+      const int64_t key = e.crossScan(*this, XS_OUT, DA_MOVE, list, i, cands, FILTER_NONE, false);
       const size_t N = cands.size();
       const size_t kEnd = key < 0 ? list.size() : i + (size_t)(key / (int64_t)std::max<size_t>(N, 1));
       const bool newOnly = m.numNew > 0 && !e.opt.anyRequested;
@@ -1258,7 +1258,7 @@ class TopicReplicaDistribution : public GoalImpl {
         seq = &inorder;
       }
       const std::vector<int32_t>& cl = e.eligibleView(*seq, DA_MOVE, cands);
-      const int64_t key = e.crossScan(*this, DA_MOVE, list, i, cl, FILTER_NONE, true, end);
+      const int64_t key = e.crossScan(*this, XS_OUT, DA_MOVE, list, i, cl, FILTER_NONE, true, end);
       if (key < 0) {
         if (runOffline) wasUnable = true;
         i = end;
@@ -1315,7 +1315,7 @@ class TopicReplicaDistribution : public GoalImpl {
         if (m.rInOff[r]) nOff++;
       size_t i = 0;
       while (i < toMove.size()) {
-        const int64_t key = cands.empty() ? -1 : e.crossScan(*this, DA_MOVE, toMove, i, cands);
+        const int64_t key = cands.empty() ? -1 : e.crossScan(*this, XS_IN, DA_MOVE, toMove, i, cands);
         if (key < 0) break;
         const size_t k = i + (size_t)key;
         const bool wasOffline = m.curOffline(toMove[k]);
@@ -1582,7 +1582,7 @@ class TopicLeaderReplicaDistribution : public GoalImpl {
         if (idOrdered(list[j])) {
           size_t j2 = j + 1;
           while (j2 < kL && idOrdered(list[j2])) ++j2;
-          const int64_t key = e.crossScan(*this, DA_MOVE, list, j, idElig, FILTER_NONE, false, j2);
+          const int64_t key = e.crossScan(*this, XS_OUT, DA_MOVE, list, j, idElig, FILTER_NONE, false, j2);
           const size_t N = idElig.size(), last = key >= 0 ? j + (size_t)(key / (int64_t)N) : j2;
           for (size_t k = j; k < last; ++k)
             visited += e.visitCount(DA_MOVE, list[k], idElig.data(), N, true);
@@ -1595,7 +1595,7 @@ class TopicLeaderReplicaDistribution : public GoalImpl {
           j = j2;
         } else {
           ownMoves(list[j], own);
-          const int64_t key = e.crossScan(*this, DA_MOVE, list, j, own, FILTER_NONE, false, j + 1);
+          const int64_t key = e.crossScan(*this, XS_OUT2, DA_MOVE, list, j, own, FILTER_NONE, false, j + 1);
           visited += e.visitCount(DA_MOVE, list[j], own.data(), key >= 0 ? (size_t)key + 1 : own.size());
           if (key >= 0) {
             winRow = j;
@@ -1701,7 +1701,7 @@ class TopicLeaderReplicaDistribution : public GoalImpl {
         }
         int64_t key = -1;
         if (act == DA_MOVE) {
-          if (!candMove.empty()) key = e.crossScan(*this, DA_MOVE, rows, 0, candMove);
+          if (!candMove.empty()) key = e.crossScan(*this, XS_IN, DA_MOVE, rows, 0, candMove);
         } else if (!candLead.empty()) {
           pbs.assign(rows.size(), dest);
           key = e.pairScan(*this, PS_TLD_IN, rows, pbs, DA_LEADERSHIP, true);
@@ -1988,7 +1988,7 @@ class LeaderReplicaDistribution : public GoalImpl {
         seq = &inorder;
       }
       const std::vector<int32_t>& cl = e.eligibleView(*seq, DA_MOVE, cands);
-      const int64_t key = e.crossScan(*this, DA_MOVE, list, i, cl);
+      const int64_t key = e.crossScan(*this, XS_OUT, DA_MOVE, list, i, cl);
       e.dev->idleWork = nullptr;  // the remaining puts, if the tree is needed, are finished below
       if (key < 0) break;
       const size_t N = cl.size();
@@ -2094,7 +2094,7 @@ class LeaderReplicaDistribution : public GoalImpl {
         (void)m.snapshotInShared(snapTab, src, s);
         return true;
       };
-      const int64_t key = cands.empty() ? -1 : e.crossScanSegs(*this, DA_MOVE, segs, cands);
+      const int64_t key = cands.empty() ? -1 : e.crossScanSegs(*this, XS_SEGS, DA_MOVE, segs, cands);
       e.dev->idleWork = nullptr;
       if (key < 0) {
         target = std::min<size_t>(target * 8, (size_t)1 << 18);
@@ -2805,7 +2805,7 @@ class BrokerSetAware : public GoalImpl {
       javaHashSetOrder(ins, order);  // Collectors.toSet()
       e.eligible(order, DA_MOVE, cands);
       one[0] = r;
-      const int64_t key = cands.empty() ? -1 : e.crossScan(*this, DA_MOVE, one, 0, cands);
+      const int64_t key = cands.empty() ? -1 : e.crossScan(*this, XS_OUT, DA_MOVE, one, 0, cands);
       if (key < 0)
         throw OptimizationFailure("[" + name + "] Cannot move replica " + m.topicNames[m.pTopic[m.rPart[r]]] + "-" +
                                       std::to_string(m.pNumber[m.rPart[r]]) + " on broker " + std::to_string(m.bId[b]) +

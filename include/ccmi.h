@@ -775,6 +775,14 @@ typedef struct ccmi_host_prefix_counters {
   int64_t host_candidates; /* candidates evaluated on the host, those of prefixes that missed included */
 } ccmi_host_prefix_counters;
 ccmi_status ccmi_host_prefix_perf(const ccmi_session* s, ccmi_host_prefix_counters* out);
+/* The same for cross scans (additive at ABI v13 too; host_scans / host_candidates above stay pair-only). A cross scan's
+ * first CCMI_HOST_PREFIX_CROSS candidates in key order (row-major: row k, column j, key k * N + j) are evaluated on
+ * the host; a scan they decide posts nothing, a miss posts the whole scan. ccmi_perf_reset clears these too. */
+typedef struct ccmi_host_cross_counters {
+  int64_t host_cross_scans;      /* cross scans decided on the host: a winner within the prefix, or K * N within it */
+  int64_t host_cross_candidates; /* candidates evaluated on the host, those of prefixes that missed included */
+} ccmi_host_cross_counters;
+ccmi_status ccmi_host_cross_perf(const ccmi_session* s, ccmi_host_cross_counters* out);
 
 #ifdef __cplusplus
 }
