@@ -224,6 +224,21 @@ class PartitionLoadRecordStruct(C.Structure):  # ccmi_partition_load_record, 80 
                 ("brokers", C.c_int32 * 8), ("reserved", C.c_int32 * 2)]
 
 
+class ProposalRecordStruct(C.Structure):  # ccmi_proposal_record, 160 bytes
+    _fields_ = [("partition", C.c_int32), ("size", C.c_int32), ("old_leader", C.c_int32),
+                ("old_leader_disk", C.c_int32), ("num_replicas", C.c_int32), ("flags", C.c_int32),
+                ("num_to_add", C.c_int32), ("num_between_disks", C.c_int32),
+                ("old_replicas", C.c_int32 * 8), ("new_replicas", C.c_int32 * 8),
+                ("old_disks", C.c_int32 * 8), ("new_disks", C.c_int32 * 8)]
+
+
+class ProposalSummaryStruct(C.Structure):  # ccmi_proposal_summary, 64 bytes
+    _fields_ = [("num_proposals", C.c_int64), ("num_inter_broker_replica_movements", C.c_int64),
+                ("inter_broker_data_to_move_mb", C.c_int64), ("num_intra_broker_replica_movements", C.c_int64),
+                ("intra_broker_data_to_move_mb", C.c_int64), ("num_leadership_movements", C.c_int64),
+                ("reserved", C.c_int64 * 2)]
+
+
 # ----------------------------------------------------------------------------------------------- errors
 class CruiseControlError(RuntimeError):
     pass
@@ -261,7 +276,7 @@ EXPORTED_SYMBOLS = (
     "ccmi_session_apply", "ccmi_last_failure_provision",
     "ccmi_compute_cluster_stats", "ccmi_broker_stats", "ccmi_partition_load", "ccmi_action_log_count", "ccmi_action_log_copy", "ccmi_replica_distribution",
     "ccmi_leader_distribution", "ccmi_replica_disks", "ccmi_proposal_count", "ccmi_proposals",
-    "ccmi_proposal_disks", "ccmi_perf", "ccmi_perf_reset", "ccmi_host_prefix_perf", "ccmi_host_cross_perf",
+    "ccmi_proposal_disks", "ccmi_proposal_diff", "ccmi_perf", "ccmi_perf_reset", "ccmi_host_prefix_perf", "ccmi_host_cross_perf",
     "ccmi_set_kernel_timing", "ccmi_session_set_shard", "ccmi_rccl_unique_id", "ccmi_session_attach_rccl",
     "ccmi_session_attach_shm", "ccmi_session_attach_shm_job", "ccmi_shard_group_create", "ccmi_shard_group_destroy", "ccmi_session_attach_group",
     "ccmi_topic_broker_set",
@@ -327,6 +342,10 @@ class Library:
         if self.has_partition_load:
             L.ccmi_partition_load.argtypes = [C.c_void_p, C.POINTER(PartitionLoadQueryStruct), C.c_void_p,
                                               C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        self.has_proposal_diff = hasattr(L, "ccmi_proposal_diff")
+        if self.has_proposal_diff:
+            L.ccmi_proposal_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                                             C.POINTER(ProposalSummaryStruct)]
         L.ccmi_session_apply.argtypes = [C.c_void_p, C.POINTER(ActionStruct), C.c_int64, C.POINTER(C.c_int64)]
         L.ccmi_last_failure_provision.argtypes = [C.c_void_p, C.POINTER(ProvisionRespStruct)]
         L.ccmi_compute_cluster_stats.argtypes = [C.c_void_p, C.POINTER(ConstraintStruct), C.POINTER(OptionsStruct),
@@ -802,6 +821,40 @@ class PartitionLoadState:
                 and self.records.tobytes() == other.records.tobytes())
 
     __hash__ = None
+
+
+class ProposalDiff:
+    """AnalyzerUtils.getDiff of the session's current model against its initial placement, as ccmi_proposal_diff
+    computed it on the device. `records` is a numpy structured array with the fields of ProposalRecordStruct in
+    ascending partition order (the first `capacity` of them), `summary` a ProposalSummaryStruct over every proposal,
+    returned or not."""
+
+    def __init__(self, records, summary: ProposalSummaryStruct):
+        self.records = records
+        self.summary = summary
+
+    @property
+    def num_proposals(self) -> int:
+        return int(self.summary.num_proposals)
+
+    @property
+    def proposals(self) -> List[ExecutionProposal]:
+        """The returned records as ExecutionProposals: what ClusterModel.proposals() lists."""
+        out = []
+        for r in self.records:
+            n = int(r["num_replicas"])
+            out.append(ExecutionProposal(int(r["partition"]), int(r["size"]), int(r["old_leader"]),
+                                         [int(x) for x in r["old_replicas"][:n]],
+                                         [int(x) for x in r["new_replicas"][:n]],
+                                         [int(x) for x in r["old_disks"][:n]], [int(x) for x in r["new_disks"][:n]]))
+        return out
+
+    def movement_stats(self) -> List[int]:
+        """OptimizerResult.getMovementStats, in the order of OptimizerResult.movement_stats."""
+        s = self.summary
+        return [int(s.num_inter_broker_replica_movements), int(s.inter_broker_data_to_move_mb),
+                int(s.num_intra_broker_replica_movements), int(s.intra_broker_data_to_move_mb),
+                int(s.num_leadership_movements)]
 
 
 class OptimizerResult:
@@ -1523,6 +1576,29 @@ class ClusterModel:
         return PartitionLoadState(records[:nrec.value], nsel.value, self.topic_names(),
                                   np.ctypeslib.as_array(d.partition_topic, shape=(P,)).copy() if P else [],
                                   np.ctypeslib.as_array(d.partition_number, shape=(P,)).copy() if P else [], ids)
+
+    def proposal_diff(self, capacity: Optional[int] = None, summary_only: bool = False) -> "ProposalDiff":
+        """The ExecutionProposals of the session's current model against its initial placement and their movement
+        statistics, diffed on the device (ccmi_proposal_diff). `capacity` cuts the records (the summary always covers
+        every proposal); None asks for the count first and then for all of them; `summary_only` returns no records.
+        The session is not changed, and the list ClusterModel.proposals() reads is left alone."""
+        import numpy as np
+
+        if not self.lib.has_proposal_diff:
+            self._not_exported("ccmi_proposal_diff", "the diff is computed on the device only")
+        if capacity is not None and capacity < 0:
+            raise IllegalArgumentException("capacity < 0")
+        fn = self.lib.lib.ccmi_proposal_diff
+        summary, n = ProposalSummaryStruct(), C.c_int64(0)
+        sized = capacity is None and not summary_only
+        if sized:  # the sizing call
+            self._checked(fn(self.handle, None, 0, C.byref(n), C.byref(summary)))
+        cap = 0 if summary_only else int(summary.num_proposals if sized else capacity)
+        records = np.zeros(min(cap, self.desc.num_partitions), dtype=np.dtype(ProposalRecordStruct))
+        if len(records) or not sized:
+            self._checked(fn(self.handle, records.ctypes.data if len(records) else None, len(records), C.byref(n),
+                             C.byref(summary)))
+        return ProposalDiff(records[:n.value], summary)
 
     def apply(self, actions) -> int:
         """Apply actions decided elsewhere (tuples in the action-log layout: type, partition, source,

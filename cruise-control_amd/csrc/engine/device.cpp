@@ -297,6 +297,9 @@ Device::~Device() {
   for (void* p : plAllocs_)  // partitionLoad (device_accept.cpp)
     if (p) (void)hipFree(p);
   if (dPlOut_) (void)hipFree(dPlOut_);
+  for (void* p : pdAllocs_)  // proposalDiff (device_accept.cpp)
+    if (p) (void)hipFree(p);
+  if (dPdOut_) (void)hipFree(dPdOut_);
   if (hStage_) (void)hipHostFree(hStage_);
   if (hResult_) (void)hipHostFree(hResult_);
   if (ev0_) (void)hipEventDestroy(EV0);

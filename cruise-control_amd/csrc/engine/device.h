@@ -23,6 +23,8 @@
 struct ccmi_basic_stats;  // include/ccmi.h
 struct ccmi_disk_stats;
 struct ccmi_partition_load_record;
+struct ccmi_proposal_record;
+struct ccmi_proposal_summary;
 
 namespace ccmi {
 
@@ -306,6 +308,21 @@ class Device {
   void partitionLoad(const PlQuery& q, const uint8_t* topicSel, const uint8_t* brokerSel, const int32_t* tieRank,
                      ccmi_partition_load_record* records, int64_t* numRecords, int64_t* numSelected);
 
+  // K14 (kernels/proposal_diff.hip, device_accept.cpp): AnalyzerUtils.getDiff of the resident model against the
+  // session's initial placement, and OptimizerResult.getMovementStats over the result. uploadInitialPlacement once per
+  // session: the initial broker of every slot [R], the initial leader's broker [P] and, on a model with disks, the
+  // initial disk of every slot [R] and of the leader [P]. proposalDiff: the pending row updates and the pending chain
+  // loads (syncChainLoads) reach the tables first; curDisks[R] is the current disk of every slot (null exactly when the
+  // model has no disks: disks are not resident); records has room for min(capacity, P) rows, the first
+  // min(capacity, proposals) are written in ascending partition order; summary may be null. Two stream syncs at most
+  // (the summary, then the rows when there are any). Counts into perf.statsLaunches / statsKernelMs / statsBytes. Not
+  // in the test emulation.
+  bool initialPlacementUploaded() const { return dPdInitDist_ != nullptr; }
+  void uploadInitialPlacement(const int32_t* initDist, const int32_t* initLeaders, const int32_t* initDisks,
+                              const int32_t* initLeaderDisks);
+  void proposalDiff(const int32_t* curDisks, ccmi_proposal_record* records, int64_t capacity, int64_t* numRecords,
+                    ccmi_proposal_summary* summary);
+
   // Disks (JBOD): the static disk / replica tables once per session; setDiskUtil whenever the host changed a disk's
   // utilization; intraRun = one intra-broker goal (K6); statsDisks = the disk part of ClusterModelStats.
   void uploadDisks(int D, const int32_t* bDiskOff, const int32_t* bDisks, const double* dCap, const uint8_t* dAlive,
@@ -468,6 +485,15 @@ class Device {
   ccmi_partition_load_record* dPlOut_ = nullptr;
   size_t plOutCap_ = 0;
   std::vector<void*> plAllocs_;
+  // proposalDiff: the initial placement (static), the current disks of a call [R], the [tiles + 1] tile counts, the
+  // sums and the output rows (grown to the largest capacity so far)
+  int32_t *dPdInitDist_ = nullptr, *dPdInitLeaders_ = nullptr, *dPdInitDisks_ = nullptr, *dPdInitLeaderDisks_ = nullptr;
+  int32_t* dPdCurDisks_ = nullptr;
+  uint32_t* dPdCounts_ = nullptr;
+  PdSums* dPdSums_ = nullptr;
+  ccmi_proposal_record* dPdOut_ = nullptr;
+  size_t pdOutCap_ = 0;
+  std::vector<void*> pdAllocs_;
   // the pending chain loads (lrows / srows) go to the device's Java loads and slot order outside a chain
   void syncChainLoads();
   int32_t* dRackRes_ = nullptr;  // rackRowsGroups results (+ the evaluated-candidate counter after them)

@@ -1,8 +1,8 @@
 // Device::acceptBatch, Device::maskBatch and Device::swapGridBatch (device.h): the launchers of K9 accept_actions
 // (kernels/accept.hip), K10 accept_mask (kernels/accept_mask.hip) and K11 accept_swaps (kernels/accept_swap.hip), which
 // share one chunk protocol (Device::acceptChunk); and Device::brokerStats, the launcher of K12
-// (kernels/broker_stats.hip), and Device::partitionLoad, the launcher of K13 (kernels/partition_load.hip), which share
-// its scope and timing. A translation unit of its own, linked into libccmi.so only: the test emulation of Device has
+// (kernels/broker_stats.hip), Device::partitionLoad, the launcher of K13 (kernels/partition_load.hip), and
+// Device::proposalDiff, the launcher of K14 (kernels/proposal_diff.hip), which share its scope and timing. A translation unit of its own, linked into libccmi.so only: the test emulation of Device has
 // none of these kernels.
 #include <hip/hip_runtime.h>
 
@@ -36,6 +36,8 @@ hipError_t launchSyncLoads(const ChainTables& C, const LoadRow* lrows, int nl, c
 hipError_t launchPartitionLoad(const PlTables& T, const PlQuery& q, PlState* st, PlEntry* bufA, PlEntry* bufB,
                                uint32_t* counts, int tiles, int slots, ccmi_partition_load_record* out, int cap,
                                int* launches, hipStream_t stream);
+hipError_t launchProposalDiff(const PdTables& T, uint32_t* counts, int tiles, PdSums* sums, ccmi_proposal_record* out,
+                              int cap, int* launches, hipStream_t stream);
 
 namespace {
 constexpr double kAcceptWaitSeconds = 120.0;
@@ -365,6 +367,99 @@ void Device::partitionLoad(const PlQuery& q, const uint8_t* topicSel, const uint
                      (int64_t)slots * (int64_t)P_ * 3 * (int64_t)sizeof(PlEntry) +
                      nrec * (int64_t)(sizeof(PlEntry) + sizeof(PartitionRec) + sizeof(LoadVec) +
                                       sizeof(ccmi_partition_load_record));
+  addKernelMs(perf.statsKernelMs);
+}
+
+void Device::uploadInitialPlacement(const int32_t* initDist, const int32_t* initLeaders, const int32_t* initDisks,
+                                    const int32_t* initLeaderDisks) {
+  DeviceGuard cur(ordinal_);
+  stopServer();
+  if (dPdInitDist_) throw std::logic_error("uploadInitialPlacement: once per session");
+  if (P_ < 1 || R_ < 1 || !initDist || !initLeaders || (D_ > 0 && (!initDisks || !initLeaderDisks)))
+    throw std::logic_error("uploadInitialPlacement: arguments");
+  auto put = [&](int32_t** d, const int32_t* h, size_t n, const char* what) {
+    hipCheck(hipMalloc((void**)d, n * sizeof(int32_t)), what);
+    pdAllocs_.push_back(*d);
+    hipCheck(hipMemcpy(*d, h, n * sizeof(int32_t), hipMemcpyHostToDevice), what);
+  };
+  put(&dPdInitLeaders_, initLeaders, (size_t)P_, "upload initial leaders");
+  if (D_ > 0) {
+    put(&dPdInitDisks_, initDisks, (size_t)R_, "upload initial disks");
+    put(&dPdInitLeaderDisks_, initLeaderDisks, (size_t)P_, "upload initial leader disks");
+  }
+  put(&dPdInitDist_, initDist, (size_t)R_, "upload initial placement");  // last: initialPlacementUploaded()
+}
+
+void Device::proposalDiff(const int32_t* curDisks, ccmi_proposal_record* records, int64_t capacity, int64_t* numRecords,
+                          ccmi_proposal_summary* summary) {
+  PlainLaunch call(*this);
+  if (!dPdInitDist_) throw std::logic_error("proposalDiff before uploadInitialPlacement");
+  if (!numRecords || capacity < 0 || (D_ > 0) != (curDisks != nullptr)) throw std::logic_error("proposalDiff: arguments");
+  const int cap = (int)std::min<int64_t>(capacity, P_);
+  if (cap > 0 && !records) throw std::logic_error("proposalDiff: no room for the records");
+  const hipStream_t st = (hipStream_t)st_;
+  const int tiles = (P_ + kPdTile - 1) / kPdTile;
+  if (!dPdSums_) {  // first use: the tile counts, the current disks, the sums
+    auto get = [&](auto** d, size_t n, const char* what) {
+      hipCheck(hipMalloc((void**)d, std::max<size_t>(1, n) * sizeof(**d)), what);
+      pdAllocs_.push_back(*d);
+    };
+    get(&dPdCounts_, (size_t)tiles + 1, "hipMalloc proposal tile counts");
+    if (D_ > 0) get(&dPdCurDisks_, (size_t)R_, "hipMalloc current disks");
+    get(&dPdSums_, 1, "hipMalloc proposal sums");  // last: marks the first use done
+  }
+  if ((size_t)cap > pdOutCap_) {
+    if (dPdOut_) hipCheck(hipFree(dPdOut_), "hipFree");
+    dPdOut_ = nullptr;
+    pdOutCap_ = 0;
+    hipCheck(hipMalloc((void**)&dPdOut_, (size_t)cap * sizeof(ccmi_proposal_record)), "hipMalloc proposal records");
+    pdOutCap_ = (size_t)cap;
+  }
+  // the device's tables current: the pending row updates (prep) and the pending slot orders and leaders (sync_loads)
+  syncChainLoads();
+  if (curDisks)
+    hipCheck(hipMemcpyAsync(dPdCurDisks_, curDisks, (size_t)R_ * sizeof(int32_t), hipMemcpyHostToDevice, st),
+             "upload current disks");
+  PdTables T;
+  T.parts = parts_;
+  T.replicas = replicas_;
+  T.pOff = dPOff_;
+  T.pSlots = dPSlots_;
+  T.pLeader = dPLeader_;
+  T.initDist = dPdInitDist_;
+  T.initLeaders = dPdInitLeaders_;
+  T.initDisks = curDisks ? dPdInitDisks_ : nullptr;
+  T.initLeaderDisks = curDisks ? dPdInitLeaderDisks_ : nullptr;
+  T.curDisks = curDisks ? dPdCurDisks_ : nullptr;
+  T.R = R_;
+  T.P = P_;
+  int launches = 0;
+  timedLaunch([&] {
+    hipCheck(launchProposalDiff(T, dPdCounts_, tiles, dPdSums_, dPdOut_, cap, &launches, st), "proposal_diff");
+  });
+  static_assert(sizeof(PdSums) == sizeof(ccmi_proposal_summary), "the device sums are the summary");
+  ccmi_proposal_summary sum;
+  hipCheck(hipMemcpyAsync(&sum, dPdSums_, sizeof(sum), hipMemcpyDeviceToHost, st), "D2H proposal summary");
+  streamWait("proposal_diff", kAcceptWaitSeconds);
+  perf.syncs++;
+  const int64_t nrec = std::min<int64_t>(sum.num_proposals, cap);
+  if (nrec > 0) {
+    hipCheck(hipMemcpyAsync(records, dPdOut_, (size_t)nrec * sizeof(ccmi_proposal_record), hipMemcpyDeviceToHost, st),
+             "D2H proposal records");
+    streamWait("proposal_diff records", kAcceptWaitSeconds);
+    perf.syncs++;
+  }
+  *numRecords = nrec;
+  if (summary) *summary = sum;
+  // a statistics read-back, as brokerStats: per partition and pass (flags, and gather when records are wanted) its
+  // record, offsets, leader id, the leader's replica record words, the initial brokers and leader and, with disks, three
+  // more words per slot; a count per tile; a row out per returned record
+  const int64_t passes = cap > 0 ? 2 : 1;
+  const int64_t slotWords = curDisks ? 4 : 1;
+  perf.statsLaunches += launches;
+  perf.statsBytes += passes * ((int64_t)P_ * (int64_t)(sizeof(PartitionRec) + 8 + 4 + 32 + 4 + (curDisks ? 4 : 0)) +
+                               (int64_t)R_ * 4 * slotWords) +
+                     (int64_t)tiles * 12 + nrec * (int64_t)sizeof(ccmi_proposal_record);
   addKernelMs(perf.statsKernelMs);
 }
 

@@ -287,6 +287,29 @@ struct PlTables {
   int32_t B, R, P, T, W;
 };
 
+// ccmi_proposal_diff (kernels/proposal_diff.hip): AnalyzerUtils.getDiff of the resident model against the session's
+// initial placement. A workgroup takes tiles of kPdTile consecutive partitions; counts[tile] is the tile's number of
+// changed partitions, after the scan the number in the tiles before it, and counts[tiles] the total. PdSums is
+// ccmi_proposal_summary as the device adds it up (v[0], the proposal count, is the scan's total).
+constexpr int kPdTile = 1024;  // partitions per workgroup: at most 2048, a multiple of 256
+static_assert(kPdTile <= 2048 && kPdTile % 256 == 0, "kPdTile");
+struct PdSums {
+  unsigned long long v[8];  // proposals, inter-broker movements, inter MB, intra-broker movements, intra MB, leadership
+};
+struct PdTables {
+  const PartitionRec* parts;
+  const ReplicaRec* replicas;
+  const int32_t* pOff;             // [P+1]
+  const int32_t* pSlots;           // [R] replica ids in Partition._replicas order
+  const int32_t* pLeader;          // [P] the leader's replica id
+  const int32_t* initDist;         // [R] initial broker of every slot
+  const int32_t* initLeaders;      // [P] initial leader's broker
+  const int32_t* initDisks;        // [R] initial disk of every slot; null without disks
+  const int32_t* initLeaderDisks;  // [P] initial leader's disk; null without disks
+  const int32_t* curDisks;         // [R] current disk of every slot (sent with the call); null without disks
+  int32_t R, P;
+};
+
 struct UpdateList {
   const BrokerRow* brows;
   const ReplicaRow* rrows;

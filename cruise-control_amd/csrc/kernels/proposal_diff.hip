@@ -1,0 +1,308 @@
+// gfx950 kernels for the proposal diff (ccmi_proposal_diff): AnalyzerUtils.getDiff (AnalyzerUtils.java:63-93) of the
+// resident model against the session's initial placement, the ExecutionProposal sets of ExecutionProposal.java:72-78 and
+// the sums of OptimizerResult.getMovementStats (OptimizerResult.java:258-278), read from the partition records, the
+// replica records, the slot order and the leaders that the chain tables keep current.
+//
+// K14 proposal_diff_flags  : grid-stride over tiles of kPdTile partitions, the lanes of a workgroup take a tile 256 at
+//                            a time in order. Per partition: its PartitionRec (the current brokers in slot order), the
+//                            initial brokers and disks, the leader's replica id and its ReplicaRec -> changed or not,
+//                            and its share of the five movement sums. One changed-count per tile; the sums go wave ->
+//                            LDS -> one set of 64-bit global integer atomics per workgroup (order-free).
+//     proposal_diff_scan   : one workgroup: exclusive scan of the tile counts in place; counts[tiles] and the
+//                            summary's proposal count get the total.
+//     proposal_diff_gather : per tile with changed partitions below the capacity, "changed" is recomputed; the rank of
+//                            a changed partition is the tile's offset + the changed ones of the rounds before it in
+//                            the tile + those of the waves before it in the round (LDS) + the lanes below it in the
+//                            64-bit ballot mask, so the compaction is stable in partition order. A lane whose rank is
+//                            below the capacity writes its 160-byte record with ten 16-byte stores.
+// Every launch is a kernel boundary on the session stream; no workgroup reads another's writes inside a launch.
+// Integer work only apart from the narrowing of the partition size; no scratch.
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "ccmi.h"
+#include "../engine/devtypes.h"
+
+namespace ccmi {
+
+namespace {
+
+constexpr int kPdBlock = 256;  // 4 waves
+constexpr int kPdWaves = kPdBlock / 64;
+constexpr int kPdRounds = kPdTile / kPdBlock;
+constexpr int kPdMaxBlocks = 1024;
+constexpr int kPdScanBlock = 1024;
+constexpr int kPdSums = 5;  // inter-broker movements and MB, intra-broker movements and MB, leadership movements
+
+static_assert(sizeof(ccmi_proposal_record) == 160 && sizeof(ccmi_proposal_summary) == 64 && sizeof(PdSums) == 64,
+              "record sizes");
+static_assert(kMaxRf == 8, "ccmi_proposal_record has eight slots");
+static_assert(R_DISK == 3 && offsetof(ReplicaRec, util) == 0 && offsetof(ReplicaRec, broker) == 32,
+              "pdDiff reads util[R_DISK] and broker by their 16-byte words");
+
+// (int) of a double as Java narrows it (JLS 5.1.3): toward zero, saturating, NaN -> 0
+__device__ __forceinline__ int32_t pdJavaInt(double x) {
+  if (x != x) return 0;
+  if (x >= 2147483647.0) return INT32_MAX;
+  if (x <= -2147483648.0) return INT32_MIN;
+  return (int32_t)x;
+}
+
+// One partition's proposal, in registers. `changed` is getDiff's test (:80); the rest is meaningful when it holds.
+struct PdRow {
+  bool changed;
+  int32_t n, size, oldLeader, oldLeaderDisk, flags, nAdd, nRemove, nBetween;
+  int32_t oldR[kMaxRf], newR[kMaxRf], oldD[kMaxRf], newD[kMaxRf];
+};
+
+__device__ __forceinline__ void pdDiff(const PdTables& T, int p, PdRow& w) {
+  const PartitionRec rec = T.parts[p];  // 64 bytes, aligned: four 16-byte loads
+  const int a = T.pOff[p];
+  const int n = max(0, min(min(T.pOff[p + 1] - a, (int)kMaxRf), T.R - a));
+  const int lr = T.pLeader[p];
+  const bool disks = T.curDisks != nullptr;
+  // the leader: its broker and DISK utilization from its replica record (util[2..3] and {broker, part, orig, flags} are
+  // the second and third 16 bytes), its disk from the slot that holds its replica id (getDiff's indexOf, not "slot 0")
+  int lb = rec.brokers[0], ld = -1;
+  double du = 0.0;
+  if ((unsigned)lr < (unsigned)T.R) {
+    const uint4* q = reinterpret_cast<const uint4*>(T.replicas + lr);
+    const uint4 u23 = q[1], ids = q[2];
+    du = __longlong_as_double((long long)(((unsigned long long)u23.w << 32) | u23.z));
+    lb = (int)ids.x;
+  }
+  bool differs = false;
+#pragma unroll
+  for (int k = 0; k < kMaxRf; ++k) {
+    const bool in = k < n;
+    w.oldR[k] = in ? T.initDist[a + k] : -1;
+    w.newR[k] = in ? rec.brokers[k] : -1;
+    w.oldD[k] = in && disks ? T.initDisks[a + k] : -1;
+    w.newD[k] = in && disks ? T.curDisks[a + k] : -1;
+    if (in && disks && T.pSlots[a + k] == lr) ld = w.newD[k];
+    differs = differs || w.oldR[k] != w.newR[k] || w.oldD[k] != w.newD[k];
+  }
+  w.n = n;
+  w.size = pdJavaInt(du);
+  w.oldLeader = T.initLeaders[p];
+  w.oldLeaderDisk = disks ? T.initLeaderDisks[p] : -1;
+  w.changed = differs || w.oldLeader != lb || w.oldLeaderDisk != ld;
+  // finalReplicas.indexOf(the leader's placement), then that position and position 0 swap (:84-88)
+  int pos = 0;
+#pragma unroll
+  for (int k = kMaxRf - 1; k >= 0; --k) pos = (k < n && w.newR[k] == lb && w.newD[k] == ld) ? k : pos;
+  const int r0 = w.newR[0], d0 = w.newD[0];
+  int rp = r0, dp = d0;
+#pragma unroll
+  for (int k = 1; k < kMaxRf; ++k) {
+    rp = k == pos ? w.newR[k] : rp;
+    dp = k == pos ? w.newD[k] : dp;
+  }
+#pragma unroll
+  for (int k = 1; k < kMaxRf; ++k) {
+    w.newR[k] = k == pos ? r0 : w.newR[k];
+    w.newD[k] = k == pos ? d0 : w.newD[k];
+  }
+  w.newR[0] = rp;
+  w.newD[0] = dp;
+  // ExecutionProposal.java:72-78 (a partition has no two replicas on one broker, so the sets count list entries)
+  int nAdd = 0, nRemove = 0, nBetween = 0;
+  bool setsDiffer = false;
+#pragma unroll
+  for (int k = 0; k < kMaxRf; ++k) {
+    bool brokerInOld = false, pairInOld = false, oldInNew = false;
+#pragma unroll
+    for (int j = 0; j < kMaxRf; ++j) {
+      const bool inj = j < n;
+      brokerInOld = brokerInOld || (inj && w.newR[k] == w.oldR[j]);
+      pairInOld = pairInOld || (inj && w.newR[k] == w.oldR[j] && w.newD[k] == w.oldD[j]);
+      oldInNew = oldInNew || (inj && w.oldR[k] == w.newR[j]);
+    }
+    if (k < n) {
+      nAdd += brokerInOld ? 0 : 1;
+      nBetween += brokerInOld && !pairInOld ? 1 : 0;
+      nRemove += oldInNew ? 0 : 1;
+      setsDiffer = setsDiffer || !pairInOld;
+    }
+  }
+  w.nAdd = nAdd;
+  w.nRemove = nRemove;
+  w.nBetween = nBetween;
+  // hasReplicaAction (:212-214), hasLeaderAction (:219-221)
+  w.flags = (setsDiffer ? 1 : 0) | ((w.oldLeader != w.newR[0] || w.oldLeaderDisk != w.newD[0]) ? 2 : 0);
+}
+
+__device__ __forceinline__ unsigned long long pdWaveSum(unsigned long long v) {
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1) v += (unsigned long long)__shfl_xor((long long)v, s, 64);
+  return v;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kPdBlock) void proposal_diff_flags(PdTables T, int tiles, uint32_t* __restrict__ counts,
+                                                                PdSums* __restrict__ sums) {
+  __shared__ uint32_t tileCnt[kPdWaves];
+  __shared__ unsigned long long sh[kPdSums];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (threadIdx.x < kPdSums) sh[threadIdx.x] = 0;
+  unsigned long long acc[kPdSums] = {0, 0, 0, 0, 0};
+  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    uint32_t cnt = 0;
+#pragma unroll 1
+    for (int k = 0; k < kPdRounds; ++k) {
+      const int p = tile * kPdTile + k * kPdBlock + (int)threadIdx.x;
+      if (p < T.P) {
+        PdRow w;
+        pdDiff(T, p, w);
+        if (w.changed) {
+          cnt++;
+          const unsigned long long size = (unsigned long long)(long long)w.size;
+          if (w.nAdd > 0 || w.nRemove > 0) {  // getMovementStats' if / else-if / else
+            acc[0] += 1;
+            acc[1] += (unsigned long long)w.nAdd * size;
+          } else if (w.nBetween > 0) {
+            acc[2] += (unsigned long long)w.nBetween;
+            acc[3] += (unsigned long long)w.nBetween * size;
+          } else {
+            acc[4] += 1;
+          }
+        }
+      }
+    }
+    cnt = (uint32_t)pdWaveSum(cnt);
+    if (lane == 0) tileCnt[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t t = 0;
+      for (int x = 0; x < kPdWaves; ++x) t += tileCnt[x];
+      counts[tile] = t;
+    }
+    __syncthreads();
+  }
+  // wave, then workgroup (LDS integer atomics: order-free), then one set of global atomics per workgroup
+#pragma unroll
+  for (int k = 0; k < kPdSums; ++k) acc[k] = pdWaveSum(acc[k]);
+  __syncthreads();  // sh is zeroed (a workgroup without a tile has not passed a barrier yet)
+  if (lane == 0)
+    for (int k = 0; k < kPdSums; ++k)
+      if (acc[k]) atomicAdd(&sh[k], acc[k]);
+  __syncthreads();
+  if (threadIdx.x < kPdSums && sh[threadIdx.x]) atomicAdd(&sums->v[1 + threadIdx.x], sh[threadIdx.x]);
+}
+
+// exclusive scan of counts[0, tiles) in place, counts[tiles] = sums->v[0] = the total: a thread sums a contiguous chunk,
+// the chunk sums are scanned in LDS, the thread writes its chunk's prefixes
+__global__ __launch_bounds__(kPdScanBlock) void proposal_diff_scan(int tiles, uint32_t* __restrict__ counts,
+                                                                   PdSums* __restrict__ sums) {
+  __shared__ uint32_t s[2][kPdScanBlock];
+  const int chunk = (tiles + kPdScanBlock - 1) / kPdScanBlock;
+  const int i0 = min(tiles, (int)threadIdx.x * chunk), i1 = min(tiles, i0 + chunk);
+  uint32_t sum = 0;
+  for (int i = i0; i < i1; ++i) sum += counts[i];
+  int cur = 0;
+  s[0][threadIdx.x] = sum;
+  __syncthreads();
+  for (int d = 1; d < kPdScanBlock; d <<= 1) {
+    const uint32_t v = s[cur][threadIdx.x] + ((int)threadIdx.x >= d ? s[cur][threadIdx.x - d] : 0u);
+    s[cur ^ 1][threadIdx.x] = v;
+    cur ^= 1;
+    __syncthreads();
+  }
+  uint32_t run = s[cur][threadIdx.x] - sum;  // exclusive
+  for (int i = i0; i < i1; ++i) {
+    const uint32_t c = counts[i];
+    counts[i] = run;
+    run += c;
+  }
+  if (threadIdx.x == kPdScanBlock - 1) {
+    counts[tiles] = s[cur][threadIdx.x];
+    sums->v[0] = s[cur][threadIdx.x];
+  }
+}
+
+__global__ __launch_bounds__(kPdBlock) void proposal_diff_gather(PdTables T, int tiles,
+                                                                 const uint32_t* __restrict__ offsets,
+                                                                 ccmi_proposal_record* __restrict__ out, int cap) {
+  __shared__ uint32_t waveCnt[kPdWaves];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    // the same for every lane of the workgroup: a tile without changed partitions, or with all of them past the capacity
+    const uint32_t first = offsets[tile], end = offsets[tile + 1];
+    if (first == end || first >= (uint32_t)cap) continue;
+    uint32_t run = first;  // the changed partitions of the tile's earlier rounds are ranked below this one's
+#pragma unroll 1
+    for (int k = 0; k < kPdRounds; ++k) {
+      const int p = tile * kPdTile + k * kPdBlock + (int)threadIdx.x;
+      PdRow w;
+      w.changed = false;
+      if (p < T.P) pdDiff(T, p, w);
+      const unsigned long long mask = __ballot(w.changed);
+      if (lane == 0) waveCnt[wave] = (uint32_t)__popcll(mask);
+      __syncthreads();
+      uint32_t before = 0, total = 0;
+#pragma unroll
+      for (int x = 0; x < kPdWaves; ++x) {
+        before += x < wave ? waveCnt[x] : 0u;
+        total += waveCnt[x];
+      }
+      const uint32_t rank = run + before + (uint32_t)__popcll(mask & below);
+      if (w.changed && rank < (uint32_t)cap) {
+        union {
+          ccmi_proposal_record r;
+          uint4 q4[10];
+        } u;
+        u.r.partition = p;
+        u.r.size = w.size;
+        u.r.old_leader = w.oldLeader;
+        u.r.old_leader_disk = w.oldLeaderDisk;
+        u.r.num_replicas = w.n;
+        u.r.flags = w.flags;
+        u.r.num_to_add = w.nAdd;
+        u.r.num_between_disks = w.nBetween;
+#pragma unroll
+        for (int x = 0; x < kMaxRf; ++x) {
+          u.r.old_replicas[x] = w.oldR[x];
+          u.r.new_replicas[x] = w.newR[x];
+          u.r.old_disks[x] = w.oldD[x];
+          u.r.new_disks[x] = w.newD[x];
+        }
+        uint4* d = reinterpret_cast<uint4*>(out + rank);
+#pragma unroll
+        for (int x = 0; x < 10; ++x) d[x] = u.q4[x];
+      }
+      run += total;
+      __syncthreads();  // waveCnt is rewritten in the next round
+    }
+  }
+}
+
+// The whole call on stream st: sums cleared, flags, scan, and the gather of at most cap records.
+hipError_t launchProposalDiff(const PdTables& T, uint32_t* counts, int tiles, PdSums* sums, ccmi_proposal_record* out,
+                              int cap, int* launches, hipStream_t stream) {
+  const bool anyDisk = T.initDisks || T.initLeaderDisks || T.curDisks;
+  const bool allDisks = T.initDisks && T.initLeaderDisks && T.curDisks;
+  if (T.P < 1 || T.R < 1 || !T.parts || !T.replicas || !T.pOff || !T.pSlots || !T.pLeader || !T.initDist ||
+      !T.initLeaders || (anyDisk && !allDisks) || !counts || !sums || tiles != (T.P + kPdTile - 1) / kPdTile || cap < 0 ||
+      cap > T.P || (cap > 0 && !out))
+    return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(sums, 0, sizeof(PdSums), stream);
+  if (e != hipSuccess) return e;
+  const int blocks = std::min(kPdMaxBlocks, tiles);
+  hipLaunchKernelGGL(proposal_diff_flags, dim3((unsigned)blocks), dim3(kPdBlock), 0, stream, T, tiles, counts, sums);
+  hipLaunchKernelGGL(proposal_diff_scan, dim3(1), dim3(kPdScanBlock), 0, stream, tiles, counts, sums);
+  int n = 2;
+  if (cap > 0) {
+    hipLaunchKernelGGL(proposal_diff_gather, dim3((unsigned)blocks), dim3(kPdBlock), 0, stream, T, tiles, counts, out,
+                       cap);
+    n++;
+  }
+  if (launches) *launches = n;
+  return hipGetLastError();
+}
+
+}  // namespace ccmi

@@ -32,6 +32,9 @@
  *   ccmi_replica_distribution / ccmi_leader_distribution
  *                              <- ClusterModel.getReplicaDistribution / getLeaderDistribution :167-198
  *   ccmi_proposals             <- AnalyzerUtils.getDiff -> Set<ExecutionProposal>  analyzer/AnalyzerUtils.java:55-93
+ *   ccmi_proposal_diff         <- AnalyzerUtils.getDiff / OptimizerResult.getMovementStats
+ *                                 analyzer/AnalyzerUtils.java:63-93, analyzer/OptimizerResult.java:258-278 (the proposals
+ *                                 and the five movement numbers of the current model, diffed on the device)
  *   ccmi_random_cluster        <- test fixture RandomCluster.generate+populate
  *                                 (src/test/java/.../model/RandomCluster.java:53-455)
  *
@@ -677,6 +680,65 @@ ccmi_status ccmi_proposals(const ccmi_session* s, int32_t max_rf, int32_t* parti
                            int32_t* old_leader, int32_t* old_out, int32_t* new_out);
 /* The logdir half of the proposals' ReplicaPlacementInfo lists (disk indices, -1 = none), same packing. */
 ccmi_status ccmi_proposal_disks(const ccmi_session* s, int32_t max_rf, int32_t* old_disk_out, int32_t* new_disk_out);
+
+/* One ExecutionProposal of the current model against the session's initial placement. 160 bytes, ten 16-byte stores.
+ * Brokers are broker indices, disks disk indices (the logdir half of ReplicaPlacementInfo). */
+typedef struct ccmi_proposal_record {
+  int32_t partition;         /* partition index (desc order) */
+  int32_t size;              /* (int) leader.load().expectedUtilizationFor(DISK) of the current leader, Java narrowing:
+                                toward zero, saturating, NaN -> 0 */
+  int32_t old_leader;        /* the initial leader's broker */
+  int32_t old_leader_disk;   /* the initial leader's disk, -1 = none */
+  int32_t num_replicas;
+  int32_t flags;             /* bit 0 hasReplicaAction: the old and new (broker, disk) sets differ
+                                (ExecutionProposal.java:212-214); bit 1 hasLeaderAction: the old leader's placement is
+                                not new_replicas[0]'s (:219-221) */
+  int32_t num_to_add;        /* |replicasToAdd|: new brokers that are not old brokers (:74) */
+  int32_t num_between_disks; /* |replicasToMoveBetweenDisksByBroker|: new (broker, disk) pairs on a kept broker that are
+                                not old pairs (:76-78) */
+  int32_t old_replicas[8];   /* the initial brokers in Partition._replicas order; unused = -1 */
+  int32_t new_replicas[8];   /* the current brokers, the leader first (getDiff :84-88: position 0 and the leader's
+                                position swap, nothing else moves); unused = -1 */
+  int32_t old_disks[8];      /* the disks of old_replicas, same order; -1 = none */
+  int32_t new_disks[8];      /* the disks of new_replicas, same order; -1 = none */
+} ccmi_proposal_record;
+/* OptimizerResult.getMovementStats (OptimizerResult.java:258-278) over every proposal. 64 bytes. */
+typedef struct ccmi_proposal_summary {
+  int64_t num_proposals;     /* all of them, whatever the capacity of the call */
+  int64_t num_inter_broker_replica_movements;
+  int64_t inter_broker_data_to_move_mb;
+  int64_t num_intra_broker_replica_movements;
+  int64_t intra_broker_data_to_move_mb;
+  int64_t num_leadership_movements;
+  int64_t reserved[2];       /* 0 */
+} ccmi_proposal_summary;
+/* Additive at ABI v13 (the capability flag is the presence of the symbol). AnalyzerUtils.getDiff (AnalyzerUtils.java:63-93)
+ * of the session's current model against the placement it was created with, and the movement statistics of the result,
+ * diffed, compacted and summed on the device from the resident tables. ccmi_proposals / ccmi_proposal_disks return the
+ * same proposals from the host's list, which only an optimization or ccmi_session_apply rebuilds; this call reads the
+ * model as it is and leaves that list alone.
+ * A partition gets a record when its current (broker, disk) list in Partition._replicas order differs from the initial
+ * one or its current leader's (broker, disk) differs from the initial leader's: the `continue` test of getDiff :80.
+ * Records come in ascending partition index, the order of ccmi_proposals.
+ * capacity is the room in records; records[0, min(capacity, num_proposals)) are written and *num_records is that
+ * minimum; nothing past it is touched. summary->num_proposals is always the whole count, so records == NULL with
+ * capacity == 0 is the summary-only call and sizes the buffer of a second one. summary may be NULL.
+ * The summary follows getMovementStats' own if / else-if / else over every proposal, returned or not: replicas to add or
+ * to remove (old brokers that are not new brokers) -> one inter-broker movement and num_to_add * size MB; else replicas
+ * between disks -> num_between_disks intra-broker movements and num_between_disks * size MB; else one leadership
+ * movement. Sums are int64.
+ * The reference's ExecutionProposal constructor throws for a proposal with both additions and between-disk moves
+ * (ExecutionProposal.java:81-84). Here such a proposal counts as inter-broker, as the if / else does, and no error is
+ * raised; the host path (ccmi_proposals and the binding's movement statistics) does the same. No goal chain of the test
+ * fixtures reaches it: a chain is broker- or disk-granularity, never both.
+ * The session is not changed. Valid on a fresh session (0 records, a zero summary), after any optimization and after
+ * ccmi_session_apply with nothing in between (the pending rows, slot orders and leaders are sent first). On a model
+ * with disks the call sends the current disk of every replica slot (4 bytes each) along; the other inputs are resident.
+ * The launches count into stats_launches, stats_bytes and stats_kernel_ms of ccmi_perf_counters, as ccmi_broker_stats.
+ * Errors, all before any launch: CCMI_E_INVALID for a NULL s, a NULL num_records, capacity < 0, or NULL records with
+ * capacity > 0 on a model with P > 0. CCMI_E_DEVICE for a device failure; on error the outputs are unspecified. */
+ccmi_status ccmi_proposal_diff(ccmi_session* s, ccmi_proposal_record* records /* [capacity] */, int64_t capacity,
+                               int64_t* num_records, ccmi_proposal_summary* summary /* optional */);
 
 /*
  * Destination-sharded mode (one process per GPU): every rank creates a session on its own device from the same
