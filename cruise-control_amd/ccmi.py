@@ -239,6 +239,18 @@ class ProposalSummaryStruct(C.Structure):  # ccmi_proposal_summary, 64 bytes
                 ("reserved", C.c_int64 * 2)]
 
 
+class SortedReplicasQueryStruct(C.Structure):  # ccmi_sorted_replicas_query, 64 bytes
+    _fields_ = [("select_mask", C.c_int32), ("num_priorities", C.c_int32), ("priorities", C.c_int32 * 2),
+                ("score_resource", C.c_int32), ("score_reverse", C.c_int32), ("above_resource", C.c_int32),
+                ("below_resource", C.c_int32), ("above_limit", C.c_double), ("below_limit", C.c_double),
+                ("topic_excluded", C.POINTER(C.c_uint8)), ("topic_included", C.POINTER(C.c_uint8))]
+
+
+# CCMI_SEL_* (ReplicaSortFunctionFactory's selection functions) and CCMI_PRIO_* (its priority functions)
+SEL_LEADERS, SEL_FOLLOWERS, SEL_ONLINE, SEL_OFFLINE, SEL_IMMIGRANTS, SEL_IMMIGRANT_OR_OFFLINE = 1, 2, 4, 8, 16, 32
+SORT_PRIORITIES = ("offline", "immigrants")  # index = CCMI_PRIO_*
+
+
 # ----------------------------------------------------------------------------------------------- errors
 class CruiseControlError(RuntimeError):
     pass
@@ -276,7 +288,7 @@ EXPORTED_SYMBOLS = (
     "ccmi_session_apply", "ccmi_last_failure_provision",
     "ccmi_compute_cluster_stats", "ccmi_broker_stats", "ccmi_partition_load", "ccmi_action_log_count", "ccmi_action_log_copy", "ccmi_replica_distribution",
     "ccmi_leader_distribution", "ccmi_replica_disks", "ccmi_proposal_count", "ccmi_proposals",
-    "ccmi_proposal_disks", "ccmi_proposal_diff", "ccmi_perf", "ccmi_perf_reset", "ccmi_host_prefix_perf", "ccmi_host_cross_perf",
+    "ccmi_proposal_disks", "ccmi_proposal_diff", "ccmi_sorted_replicas", "ccmi_perf", "ccmi_perf_reset", "ccmi_host_prefix_perf", "ccmi_host_cross_perf",
     "ccmi_set_kernel_timing", "ccmi_session_set_shard", "ccmi_rccl_unique_id", "ccmi_session_attach_rccl",
     "ccmi_session_attach_shm", "ccmi_session_attach_shm_job", "ccmi_shard_group_create", "ccmi_shard_group_destroy", "ccmi_session_attach_group",
     "ccmi_topic_broker_set",
@@ -346,6 +358,11 @@ class Library:
         if self.has_proposal_diff:
             L.ccmi_proposal_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
                                              C.POINTER(ProposalSummaryStruct)]
+        self.has_sorted_replicas = hasattr(L, "ccmi_sorted_replicas")
+        if self.has_sorted_replicas:
+            L.ccmi_sorted_replicas.argtypes = [C.c_void_p, C.POINTER(SortedReplicasQueryStruct), C.c_void_p, C.c_int64,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int64)]
         L.ccmi_session_apply.argtypes = [C.c_void_p, C.POINTER(ActionStruct), C.c_int64, C.POINTER(C.c_int64)]
         L.ccmi_last_failure_provision.argtypes = [C.c_void_p, C.POINTER(ProvisionRespStruct)]
         L.ccmi_compute_cluster_stats.argtypes = [C.c_void_p, C.POINTER(ConstraintStruct), C.POINTER(OptionsStruct),
@@ -1599,6 +1616,93 @@ class ClusterModel:
             self._checked(fn(self.handle, records.ctypes.data if len(records) else None, len(records), C.byref(n),
                              C.byref(summary)))
         return ProposalDiff(records[:n.value], summary)
+
+    def sorted_replicas(self, brokers=None, *, leaders=False, followers=False, online=False, offline=False,
+                        immigrants=False, immigrant_or_offline=False, priorities=(), score=None, reverse=False,
+                        above=None, below=None, excluded_topics=None, included_topics=None, with_scores=False):
+        """Per asked broker the list a freshly initialised SortedReplicas would iterate on the session's current model,
+        selected and sorted on the device (ccmi_sorted_replicas): one numpy int32 array [k, 2] of (partition, broker)
+        rows per broker of `brokers` (broker indices; None = every broker), usable as they stand as the sources or
+        candidates of swaps_acceptance_grid. The keyword flags are ReplicaSortFunctionFactory's selection functions,
+        `priorities` a sequence of "offline" / "immigrants" (or CCMI_PRIO_* numbers) in application order, `score` a
+        resource (name or index) scored by its metric group's average, `reverse` the reversed score, `above` / `below`
+        (resource, limit) pairs, `excluded_topics` / `included_topics` topic names (or a [T] uint8 mask). With
+        `with_scores` the result is (lists, scores): the float64 scores exactly as compared, broker by broker. The
+        buffer is sized by a first call with no room. A broker the call refuses raises IllegalArgumentException with
+        its position in `first_invalid`. The session is not changed."""
+        import numpy as np
+
+        if not self.lib.has_sorted_replicas:
+            raise UnsupportedOperationException(
+                f"{self.lib.path} does not export ccmi_sorted_replicas: the lists are built on the device only")
+        B, T = self.desc.num_brokers, self.desc.num_topics
+
+        def res(r):
+            return r if isinstance(r, int) else RESOURCES.index(r)
+
+        q = SortedReplicasQueryStruct()
+        q.select_mask = ((SEL_LEADERS if leaders else 0) | (SEL_FOLLOWERS if followers else 0) |
+                         (SEL_ONLINE if online else 0) | (SEL_OFFLINE if offline else 0) |
+                         (SEL_IMMIGRANTS if immigrants else 0) |
+                         (SEL_IMMIGRANT_OR_OFFLINE if immigrant_or_offline else 0))
+        prio = [p if isinstance(p, int) else SORT_PRIORITIES.index(p) for p in priorities]
+        if len(prio) > 2:
+            raise IllegalArgumentException("at most two priority functions")
+        q.num_priorities = len(prio)
+        q.priorities[0], q.priorities[1] = (prio + [-1, -1])[:2]
+        q.score_resource = -1 if score is None else res(score)
+        q.score_reverse = int(bool(reverse))
+        q.above_resource, q.above_limit = (-1, 0.0) if above is None else (res(above[0]), float(above[1]))
+        q.below_resource, q.below_limit = (-1, 0.0) if below is None else (res(below[0]), float(below[1]))
+        keep = []
+
+        def mask(topics):
+            if isinstance(topics, np.ndarray):
+                m = np.ascontiguousarray(topics, dtype=np.uint8)
+                if m.shape != (T,):
+                    raise IllegalArgumentException(f"a topic mask needs one entry per topic ({T})")
+            else:
+                wanted = set(topics)
+                m = np.array([1 if n in wanted else 0 for n in self.topic_names()], dtype=np.uint8)
+            if not len(m):
+                m = np.zeros(1, dtype=np.uint8)
+            keep.append(m)
+            return m.ctypes.data_as(C.POINTER(C.c_uint8))
+
+        if excluded_topics is not None:
+            q.topic_excluded = mask(excluded_topics)
+        if included_topics is not None:
+            q.topic_included = mask(included_topics)
+        if brokers is None:
+            ask, n = None, B
+        else:
+            ask = np.ascontiguousarray(list(brokers), dtype=np.int32).reshape(-1)
+            n = len(ask)
+        fn = self.lib.lib.ccmi_sorted_replicas
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        total, bad = C.c_int64(0), C.c_int64(-1)
+
+        def call(records, scores, capacity):
+            try:
+                self._checked(fn(self.handle, C.byref(q), ask.ctypes.data if ask is not None else None, n,
+                                 offsets.ctypes.data, records.ctypes.data if capacity else None,
+                                 scores.ctypes.data if scores is not None and capacity else None, capacity,
+                                 C.byref(total), C.byref(bad)))
+            except CruiseControlError as e:
+                e.first_invalid = bad.value
+                raise
+
+        if brokers is not None and n == 0:
+            ask = np.zeros(1, dtype=np.int32)  # n == 0 with a list: not the NULL "every broker" form
+        call(None, None, 0)  # the sizing call
+        records = np.zeros((total.value, 2), dtype=np.int32)  # ccmi_swap_replica is two int32
+        scores = np.zeros(total.value, dtype=np.float64) if with_scores else None
+        if total.value:
+            call(records, scores, total.value)
+        lists = [records[offsets[i]:offsets[i + 1]] for i in range(n)]
+        if with_scores:
+            return lists, [scores[offsets[i]:offsets[i + 1]] for i in range(n)]
+        return lists
 
     def apply(self, actions) -> int:
         """Apply actions decided elsewhere (tuples in the action-log layout: type, partition, source,

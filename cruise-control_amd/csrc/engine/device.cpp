@@ -300,6 +300,10 @@ Device::~Device() {
   for (void* p : pdAllocs_)  // proposalDiff (device_accept.cpp)
     if (p) (void)hipFree(p);
   if (dPdOut_) (void)hipFree(dPdOut_);
+  for (void* p : srAllocs_)  // sortedReplicas (device_accept.cpp)
+    if (p) (void)hipFree(p);
+  if (dSrRecords_) (void)hipFree(dSrRecords_);
+  if (dSrScores_) (void)hipFree(dSrScores_);
   if (hStage_) (void)hipHostFree(hStage_);
   if (hResult_) (void)hipHostFree(hResult_);
   if (ev0_) (void)hipEventDestroy(EV0);

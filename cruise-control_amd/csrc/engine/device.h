@@ -23,6 +23,7 @@
 struct ccmi_basic_stats;  // include/ccmi.h
 struct ccmi_disk_stats;
 struct ccmi_partition_load_record;
+struct ccmi_swap_replica;
 struct ccmi_proposal_record;
 struct ccmi_proposal_summary;
 
@@ -323,6 +324,19 @@ class Device {
   void proposalDiff(const int32_t* curDisks, ccmi_proposal_record* records, int64_t capacity, int64_t* numRecords,
                     ccmi_proposal_summary* summary);
 
+  // K15 (kernels/sorted_replicas.hip, device_accept.cpp): per asked broker the list a freshly initialised
+  // SortedReplicas of the Spec q would iterate. uploadSortedStatic once per session: Model::rStatic [R] (the rank of
+  // Replica.compareTo's tail), and the call's scratch with it. sortedReplicas: the pending row updates and the pending
+  // chain loads (syncChainLoads) reach the tables first; seg[B] maps a broker to its segment in [0, n) or -1;
+  // topicExcluded[T] and topicIncluded[T] may each be null; offsets[n + 1] and *numRecords = offsets[n] are always
+  // written; records (and scores, when not null) only when offsets[n] <= capacity. One stream sync for the offsets, one
+  // more for the rows. Counts into perf.statsLaunches / statsKernelMs / statsBytes. Not in the test emulation.
+  bool sortedStaticUploaded() const { return dSrStatic_ != nullptr; }
+  void uploadSortedStatic(const int32_t* rStatic);
+  void sortedReplicas(const SrQuery& q, const int32_t* seg, int n, const uint8_t* topicExcluded,
+                      const uint8_t* topicIncluded, int64_t* offsets, ccmi_swap_replica* records, double* scores,
+                      int64_t capacity, int64_t* numRecords);
+
   // Disks (JBOD): the static disk / replica tables once per session; setDiskUtil whenever the host changed a disk's
   // utilization; intraRun = one intra-broker goal (K6); statsDisks = the disk part of ClusterModelStats.
   void uploadDisks(int D, const int32_t* bDiskOff, const int32_t* bDisks, const double* dCap, const uint8_t* dAlive,
@@ -494,6 +508,20 @@ class Device {
   ccmi_proposal_record* dPdOut_ = nullptr;
   size_t pdOutCap_ = 0;
   std::vector<void*> pdAllocs_;
+  // sortedReplicas: the static tail ranks [R], the segment map, counts and cursors [B], {total, longest, offsets} [B + 3],
+  // the topic masks [T], the keys and segments [R], the entry buffers [R] (the second one once a segment is longer than
+  // a tile) and the output rows (grown to the largest total so far)
+  int32_t *dSrStatic_ = nullptr, *dSrSeg_ = nullptr, *dSrSegOf_ = nullptr;
+  uint32_t *dSrCounts_ = nullptr, *dSrCursor_ = nullptr;
+  unsigned long long* dSrState_ = nullptr;
+  uint8_t *dSrTopicExcl_ = nullptr, *dSrTopicIncl_ = nullptr;
+  uint64_t* dSrKeys_ = nullptr;
+  SrEntry* dSrBuf_[2] = {nullptr, nullptr};
+  ccmi_swap_replica* dSrRecords_ = nullptr;
+  double* dSrScores_ = nullptr;
+  size_t srOutCap_ = 0;
+  std::vector<void*> srAllocs_;
+  std::vector<unsigned long long> srHost_;
   // the pending chain loads (lrows / srows) go to the device's Java loads and slot order outside a chain
   void syncChainLoads();
   int32_t* dRackRes_ = nullptr;  // rackRowsGroups results (+ the evaluated-candidate counter after them)

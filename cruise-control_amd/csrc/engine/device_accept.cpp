@@ -2,8 +2,9 @@
 // (kernels/accept.hip), K10 accept_mask (kernels/accept_mask.hip) and K11 accept_swaps (kernels/accept_swap.hip), which
 // share one chunk protocol (Device::acceptChunk); and Device::brokerStats, the launcher of K12
 // (kernels/broker_stats.hip), Device::partitionLoad, the launcher of K13 (kernels/partition_load.hip), and
-// Device::proposalDiff, the launcher of K14 (kernels/proposal_diff.hip), which share its scope and timing. A translation unit of its own, linked into libccmi.so only: the test emulation of Device has
-// none of these kernels.
+// Device::proposalDiff, the launcher of K14 (kernels/proposal_diff.hip), and Device::sortedReplicas, the launcher of K15
+// (kernels/sorted_replicas.hip), which share its scope and timing. A translation unit of its own, linked into libccmi.so
+// only: the test emulation of Device has none of these kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +39,13 @@ hipError_t launchPartitionLoad(const PlTables& T, const PlQuery& q, PlState* st,
                                int* launches, hipStream_t stream);
 hipError_t launchProposalDiff(const PdTables& T, uint32_t* counts, int tiles, PdSums* sums, ccmi_proposal_record* out,
                               int cap, int* launches, hipStream_t stream);
+hipError_t launchSortedReplicasCount(const SrTables& T, const SrQuery& q, int n, uint64_t* keys, int32_t* segOf,
+                                     uint32_t* counts, uint32_t* cursor, unsigned long long* state, int* launches,
+                                     hipStream_t stream);
+hipError_t launchSortedReplicasFill(const SrTables& T, const SrQuery& q, int n, const uint64_t* keys,
+                                    const int32_t* segOf, uint32_t* cursor, const unsigned long long* state,
+                                    long long total, long long maxLen, SrEntry* bufA, SrEntry* bufB,
+                                    ccmi_swap_replica* records, double* scores, int* launches, hipStream_t stream);
 
 namespace {
 constexpr double kAcceptWaitSeconds = 120.0;
@@ -461,6 +469,120 @@ void Device::proposalDiff(const int32_t* curDisks, ccmi_proposal_record* records
                                (int64_t)R_ * 4 * slotWords) +
                      (int64_t)tiles * 12 + nrec * (int64_t)sizeof(ccmi_proposal_record);
   addKernelMs(perf.statsKernelMs);
+}
+
+
+void Device::uploadSortedStatic(const int32_t* rStatic) {
+  DeviceGuard cur(ordinal_);
+  stopServer();
+  if (dSrStatic_) throw std::logic_error("uploadSortedStatic: once per session");
+  if (R_ < 1 || B_ < 1 || !rStatic) throw std::logic_error("uploadSortedStatic: arguments");
+  auto get = [&](auto** d, size_t n, const char* what) {
+    hipCheck(hipMalloc((void**)d, std::max<size_t>(1, n) * sizeof(**d)), what);
+    srAllocs_.push_back(*d);
+  };
+  get(&dSrSeg_, (size_t)B_, "hipMalloc segment map");
+  get(&dSrCounts_, (size_t)B_, "hipMalloc segment counts");
+  get(&dSrCursor_, (size_t)B_, "hipMalloc segment cursors");
+  get(&dSrState_, (size_t)B_ + 3, "hipMalloc segment offsets");
+  get(&dSrTopicExcl_, (size_t)T_, "hipMalloc excluded topics");
+  get(&dSrTopicIncl_, (size_t)T_, "hipMalloc included topics");
+  get(&dSrKeys_, (size_t)R_, "hipMalloc replica keys");
+  get(&dSrSegOf_, (size_t)R_, "hipMalloc replica segments");
+  get(&dSrBuf_[0], (size_t)R_, "hipMalloc sort entries");
+  int32_t* d = nullptr;
+  get(&d, (size_t)R_, "hipMalloc static ranks");
+  hipCheck(hipMemcpy(d, rStatic, (size_t)R_ * sizeof(int32_t), hipMemcpyHostToDevice), "upload static ranks");
+  dSrStatic_ = d;  // last: sortedStaticUploaded()
+}
+
+void Device::sortedReplicas(const SrQuery& q, const int32_t* seg, int n, const uint8_t* topicExcluded,
+                            const uint8_t* topicIncluded, int64_t* offsets, ccmi_swap_replica* records, double* scores,
+                            int64_t capacity, int64_t* numRecords) {
+  PlainLaunch call(*this);
+  if (!dSrStatic_) throw std::logic_error("sortedReplicas before uploadSortedStatic");
+  if (!seg || n < 1 || n > B_ || !offsets || !numRecords || capacity < 0)
+    throw std::logic_error("sortedReplicas: arguments");
+  const hipStream_t st = (hipStream_t)st_;
+  // the device's tables current: the pending row updates (prep) and the pending chain loads (sync_loads)
+  syncChainLoads();
+  hipCheck(hipMemcpyAsync(dSrSeg_, seg, (size_t)B_ * sizeof(int32_t), hipMemcpyHostToDevice, st), "upload segment map");
+  if (topicExcluded)
+    hipCheck(hipMemcpyAsync(dSrTopicExcl_, topicExcluded, (size_t)T_, hipMemcpyHostToDevice, st), "upload excluded topics");
+  if (topicIncluded)
+    hipCheck(hipMemcpyAsync(dSrTopicIncl_, topicIncluded, (size_t)T_, hipMemcpyHostToDevice, st), "upload included topics");
+  SrTables T;
+  T.brokers = brokers_;
+  T.replicas = replicas_;
+  T.parts = parts_;
+  T.rLoad = dRLoad_;
+  T.rStatic = dSrStatic_;
+  T.seg = dSrSeg_;
+  T.topicExcluded = topicExcluded ? dSrTopicExcl_ : nullptr;
+  T.topicIncluded = topicIncluded ? dSrTopicIncl_ : nullptr;
+  T.B = B_;
+  T.R = R_;
+  T.P = P_;
+  T.T = T_;
+  T.W = W_;
+  int launches = 0;
+  timedLaunch([&] {
+    hipCheck(launchSortedReplicasCount(T, q, n, dSrKeys_, dSrSegOf_, dSrCounts_, dSrCursor_, dSrState_, &launches, st),
+             "sorted_replicas keys");
+  });
+  // one small read-back: the total, the longest segment and the offsets, which the caller gets whatever the capacity
+  srHost_.resize((size_t)n + 3);
+  hipCheck(hipMemcpyAsync(srHost_.data(), dSrState_, ((size_t)n + 3) * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                          st),
+           "D2H segment offsets");
+  streamWait("sorted_replicas keys", kAcceptWaitSeconds);
+  perf.syncs++;
+  addKernelMs(perf.statsKernelMs);
+  const int64_t total = (int64_t)srHost_[0], maxLen = (int64_t)srHost_[1];
+  if (total < 0 || total > R_ || maxLen > total) throw std::runtime_error("device sorted_replicas: impossible counts");
+  std::memcpy(offsets, srHost_.data() + 2, ((size_t)n + 1) * sizeof(int64_t));
+  *numRecords = total;
+  // per replica its record, the broker's alive word, the segment, the rank and (with a score) the load's windows in, a
+  // key and a segment out
+  perf.statsBytes += (int64_t)R_ * (int64_t)(sizeof(ReplicaRec) + 4 + 4 + 4 + (q.scoreRes >= 0 ? 2 * sizeof(Window) : 0) + 12) +
+                     (int64_t)n * 24;
+  if (total > 0 && total <= capacity) {
+    if (!records) throw std::logic_error("sortedReplicas: no room for the records");
+    if (maxLen > kSrSortTile && !dSrBuf_[1]) {  // a segment longer than a tile: the merge passes' second buffer
+      hipCheck(hipMalloc((void**)&dSrBuf_[1], (size_t)R_ * sizeof(SrEntry)), "hipMalloc merge buffer");
+      srAllocs_.push_back(dSrBuf_[1]);
+    }
+    if ((size_t)total > srOutCap_) {
+      if (dSrRecords_) hipCheck(hipFree(dSrRecords_), "hipFree");
+      if (dSrScores_) hipCheck(hipFree(dSrScores_), "hipFree");
+      dSrRecords_ = nullptr;
+      dSrScores_ = nullptr;
+      srOutCap_ = 0;
+      const size_t room = ((size_t)total + 1) & ~(size_t)1;  // whole 16-byte stores
+      hipCheck(hipMalloc((void**)&dSrRecords_, room * sizeof(ccmi_swap_replica)), "hipMalloc sorted records");
+      hipCheck(hipMalloc((void**)&dSrScores_, room * sizeof(double)), "hipMalloc sorted scores");
+      srOutCap_ = (size_t)total;
+    }
+    int fill = 0;
+    timedLaunch([&] {
+      hipCheck(launchSortedReplicasFill(T, q, n, dSrKeys_, dSrSegOf_, dSrCursor_, dSrState_, total, maxLen, dSrBuf_[0],
+                                        dSrBuf_[1], dSrRecords_, scores ? dSrScores_ : nullptr, &fill, st),
+               "sorted_replicas sort");
+    });
+    hipCheck(hipMemcpyAsync(records, dSrRecords_, (size_t)total * sizeof(ccmi_swap_replica), hipMemcpyDeviceToHost, st),
+             "D2H sorted records");
+    if (scores)
+      hipCheck(hipMemcpyAsync(scores, dSrScores_, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, st),
+               "D2H sorted scores");
+    streamWait("sorted_replicas sort", kAcceptWaitSeconds);
+    perf.syncs++;
+    addKernelMs(perf.statsKernelMs);
+    launches += fill;
+    // per replica a key and a segment in; per entry one write, the sort's read and write, a read and a write per merge
+    // pass, the gather's entry and replica words in and a record (and a score) out
+    perf.statsBytes += (int64_t)R_ * 12 + total * (int64_t)(sizeof(SrEntry) * (4 + 2 * (fill - 3)) + 16 + 8 + (scores ? 8 : 0));
+  }
+  perf.statsLaunches += launches;
 }
 
 }  // namespace ccmi

@@ -310,6 +310,43 @@ struct PdTables {
   int32_t R, P;
 };
 
+// ccmi_sorted_replicas (kernels/sorted_replicas.hip): a broker's SortedReplicas list per asked broker. SrEntry: one
+// selected replica in the sort; the key is Model::replicaKey generalised to the priority order (bits 63 / 62: priority
+// function 0 / 1 says "not first", 61..30: the Double.compare-ordered float score bits, 29: online, 28..0: rStatic) and
+// unique among replicas. SrQuery: the Spec of a call. SrState: the device words the host reads back with the offsets.
+constexpr int kSrSortTile = 4096;  // entries one workgroup sorts in LDS (64 KB: two workgroups per CU)
+struct alignas(16) SrEntry {
+  uint64_t key;
+  int32_t r;
+  int32_t pad;
+};
+static_assert(sizeof(SrEntry) == 16, "SrEntry is one 16-byte load");
+constexpr uint64_t kSrNotSelected = ~0ull;  // no replica's key: the score field is all ones only for a NaN
+struct SrQuery {
+  int32_t selectMask;   // CCMI_SEL_* bits
+  int32_t prio[2];      // CCMI_PRIO_* of priority function 0 / 1, -1 = none
+  int32_t scoreRes;     // Res, -1 = no score function
+  int32_t scoreReverse;
+  int32_t aboveRes, belowRes;  // Res, -1 = none
+  int32_t pad;
+  double aboveLimit, belowLimit;
+};
+struct SrState {
+  unsigned long long total;   // offsets[n]
+  unsigned long long maxLen;  // the longest segment
+};
+struct SrTables {
+  const BrokerRec* brokers;
+  const ReplicaRec* replicas;
+  const PartitionRec* parts;
+  const LoadVec* rLoad;           // [R] Replica.load() (the chain tables' copy)
+  const int32_t* rStatic;         // [R] dense rank of Replica.compareTo's tail (static)
+  const int32_t* seg;             // [B] the segment of a broker, -1 = not asked for
+  const uint8_t* topicExcluded;   // [T] or null
+  const uint8_t* topicIncluded;   // [T] or null
+  int32_t B, R, P, T, W;
+};
+
 struct UpdateList {
   const BrokerRow* brows;
   const ReplicaRow* rrows;

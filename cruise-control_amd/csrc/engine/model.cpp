@@ -822,6 +822,7 @@ bool Model::selects(const Spec& s, int r) const {
   if (s.selImmigrants && !immigrant(r)) return false;
   if (s.selImmOrOffline && !(immigrant(r) || curOffline(r))) return false;
   if (s.selOffline && !curOffline(r)) return false;
+  if (s.selOnline && curOffline(r)) return false;
   // ReplicaSortFunctionFactory.selectReplicasBasedOnExcludedTopics (:135-146)
   if (s.selExclTopics && !origOffline(r) && exclTopicSel[pTopic[rPart[r]]]) return false;
   if (s.selExclMust && !origOffline(r) && (exclTopicSel[pTopic[rPart[r]]] || mustTopicSel[pTopic[rPart[r]]])) return false;

@@ -277,6 +277,7 @@ class Model {
   struct Spec {
     bool selLeaders = false, selFollowers = false, selImmigrants = false, selImmOrOffline = false;
     bool selOffline = false;
+    bool selOnline = false;  // selectOnlineReplicas: !isCurrentOffline (CCMI_SEL_ONLINE)
     bool selExclTopics = false;  // selectReplicasBasedOnExcludedTopics over exclTopicSel
     bool selExclMust = false;    // ... over exclTopicSel + mustTopicSel (BrokerSetAwareGoal._excludedTopics)
     bool selMustTopics = false;  // selectReplicasBasedOnIncludedTopics over mustTopicSel (MinTopicLeadersPerBrokerGoal)
@@ -287,7 +288,7 @@ class Model {
     bool scoreReverse = false;
     bool operator==(const Spec& o) const {
       return selLeaders == o.selLeaders && selFollowers == o.selFollowers && selImmigrants == o.selImmigrants &&
-             selOffline == o.selOffline && selExclTopics == o.selExclTopics && selExclMust == o.selExclMust &&
+             selOffline == o.selOffline && selOnline == o.selOnline && selExclTopics == o.selExclTopics && selExclMust == o.selExclMust &&
              selMustTopics == o.selMustTopics &&
              selImmOrOffline == o.selImmOrOffline && selAboveRes == o.selAboveRes && selBelowRes == o.selBelowRes &&
              aboveLimit == o.aboveLimit && belowLimit == o.belowLimit && prioOffline == o.prioOffline &&

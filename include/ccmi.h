@@ -33,6 +33,7 @@
  *                              <- ClusterModel.getReplicaDistribution / getLeaderDistribution :167-198
  *   ccmi_proposals             <- AnalyzerUtils.getDiff -> Set<ExecutionProposal>  analyzer/AnalyzerUtils.java:55-93
  *   ccmi_proposal_diff         <- AnalyzerUtils.getDiff / OptimizerResult.getMovementStats
+ *   ccmi_sorted_replicas       <- SortedReplicas.sortedReplicas  model/SortedReplicas.java:75-114
  *                                 analyzer/AnalyzerUtils.java:63-93, analyzer/OptimizerResult.java:258-278 (the proposals
  *                                 and the five movement numbers of the current model, diffed on the device)
  *   ccmi_random_cluster        <- test fixture RandomCluster.generate+populate
@@ -739,6 +740,70 @@ typedef struct ccmi_proposal_summary {
  * capacity > 0 on a model with P > 0. CCMI_E_DEVICE for a device failure; on error the outputs are unspecified. */
 ccmi_status ccmi_proposal_diff(ccmi_session* s, ccmi_proposal_record* records /* [capacity] */, int64_t capacity,
                                int64_t* num_records, ccmi_proposal_summary* summary /* optional */);
+
+/* ReplicaSortFunctionFactory's selection functions (ReplicaSortFunctionFactory.java:29-40) and the two priority
+ * functions the inter-broker goals use (:21-23). */
+enum { CCMI_SEL_LEADERS = 1, CCMI_SEL_FOLLOWERS = 2, CCMI_SEL_ONLINE = 4, CCMI_SEL_OFFLINE = 8,
+       CCMI_SEL_IMMIGRANTS = 16, CCMI_SEL_IMMIGRANT_OR_OFFLINE = 32 };      /* ReplicaSortFunctionFactory selections */
+enum { CCMI_PRIO_OFFLINE = 0, CCMI_PRIO_IMMIGRANTS = 1 };                  /* prioritizeOfflineReplicas / prioritizeImmigrants */
+/* What a SortedReplicas is built from (SortedReplicas.java:57-96, SortedReplicasHelper). 64 bytes. */
+typedef struct ccmi_sorted_replicas_query {
+  int32_t select_mask;        /* OR of CCMI_SEL_*: every named selection must hold */
+  int32_t num_priorities;     /* 0..2 */
+  int32_t priorities[2];      /* CCMI_PRIO_* in application order (SortedReplicas._priorityFuncs); unused = -1 */
+  int32_t score_resource;     /* ccmi_resource, or -1 = no score function */
+  int32_t score_reverse;      /* 0 sortByMetricGroupValue, 1 reverseSortByMetricGroupValue */
+  int32_t above_resource;     /* selectReplicasAboveLimit resource, -1 = none */
+  int32_t below_resource;     /* selectReplicasBelowLimit resource, -1 = none */
+  double  above_limit, below_limit;
+  const uint8_t* topic_excluded;  /* [T] or NULL: selectReplicasBasedOnExcludedTopics */
+  const uint8_t* topic_included;  /* [T] or NULL: selectReplicasBasedOnIncludedTopics */
+} ccmi_sorted_replicas_query;
+/* Additive at ABI v13 (the capability flag is the presence of the symbol). The sorted replicas of brokers on the session's
+ * current model, selected, keyed and sorted on the device from the resident tables: segment i, records[offsets[i],
+ * offsets[i + 1]), is what new SortedReplicas(broker brokers[i], selections, priorities, score).sortedReplicas(false)
+ * (SortedReplicas.java:57-62, :106-114) would iterate if it were initialised now (ensureInitialize, :168-177: every replica
+ * of the broker that all selection functions accept). brokers == NULL asks for brokers 0..n-1 and needs n == B. Each
+ * record is {partition index, broker index}: a ccmi_swap_replica, usable as it stands as a source or candidate of
+ * ccmi_swaps_acceptance_grid and, with an action type, as a ccmi_move_source of ccmi_moves_acceptance_mask.
+ * Order: the comparator of SortedReplicas.java:75-90. First the priority functions in list order (comparePriority,
+ * :179-192), priorities[0] before priorities[1]: CCMI_PRIO_OFFLINE puts isCurrentOffline() replicas first, CCMI_PRIO_IMMIGRANTS
+ * replicas with originalBroker() != broker() (ReplicaSortFunctionFactory.java:21-23); either order of the two is honoured.
+ * Then, with score_resource >= 0, Double.compare of the score: (double) load().loadByWindows().valuesForGroup(the
+ * resource's metric group).avg() (ReplicaSortFunctionFactory.java:51-58; CPU: [CPU], DISK: [DISK], NW_IN: [LEADER_BYTES_IN,
+ * REPLICATION_BYTES_IN] added window by window in float, NW_OUT: [LEADER_BYTES_OUT, REPLICATION_BYTES_OUT]; avg() =
+ * (float)(sum / W)), negated for score_reverse (:65-72). Double.compare puts -0.0 below 0.0, and a reversed zero is -0.0; an
+ * empty load scores 0. Last Replica.compareTo (Replica.java:350-377): isCurrentOffline() replicas first, then the partition
+ * number, then the original broker's id, then the topic name (String.compareTo). The session ranks the topic names itself;
+ * the caller passes nothing for it. No two replicas compare equal, so the order is total. NaN loads are outside the
+ * contract. scores (optional, [capacity]): scores[k] is the score of records[k] exactly as compared, 0.0 without a score
+ * function.
+ * Selections (all must hold): CCMI_SEL_LEADERS isLeader(), CCMI_SEL_FOLLOWERS !isLeader(), CCMI_SEL_ONLINE
+ * !isCurrentOffline(), CCMI_SEL_OFFLINE isCurrentOffline(), CCMI_SEL_IMMIGRANTS originalBroker() != broker(),
+ * CCMI_SEL_IMMIGRANT_OR_OFFLINE either (ReplicaSortFunctionFactory.java:29-40); topic_excluded keeps a replica when
+ * isOriginalOffline() || !topic_excluded[topic] (:144-146: an original-offline replica passes whatever its topic);
+ * topic_included keeps it when topic_included[topic] != 0 (:153-155); above_resource / below_resource keep it when
+ * load().expectedUtilizationFor(resource) > above_limit / < below_limit, both strict (:163-175). Per-disk sorted replicas
+ * and prioritizeDiskImmigrants (the intra-broker goals) are out of scope.
+ * offsets[0..n] are always written in full and *num_records = offsets[n]. records and scores are written only when
+ * offsets[n] <= capacity; otherwise neither is touched and the status is still CCMI_OK, so capacity == 0 with NULL records
+ * is the sizing call (NULL records when there are records and they fit is CCMI_E_INVALID, found after the offsets are
+ * written). A broker with no replica, or none selected, is a zero-length segment; n == 0 is CCMI_OK.
+ * The session is not changed: tracked sorted replicas, the snapshot caches, the broker versions, the action log and the
+ * proposals stay as they are. Valid on a fresh session, after any optimization and after ccmi_session_apply with nothing
+ * in between (the pending rows, Java loads, slot orders and leaders are sent first). A sharded session answers locally.
+ * The launches count into stats_launches, stats_bytes and stats_kernel_ms of ccmi_perf_counters, as ccmi_broker_stats; no
+ * acceptance counter counts them.
+ * Errors, all before any launch: CCMI_E_INVALID for a NULL s, q, offsets or num_records, capacity < 0, unknown bits in
+ * select_mask, num_priorities outside 0..2, a priority value other than 0 or 1, a priority named twice, a resource
+ * outside [-1, 4), score_reverse not 0 or 1, brokers == NULL with n != B, and, with *first_invalid (when given) set to
+ * its position, a broker out of range or listed twice; *first_invalid is -1 for every other error and on success.
+ * CCMI_E_DEVICE for a device failure. On error the outputs are unspecified. */
+ccmi_status ccmi_sorted_replicas(ccmi_session* s, const ccmi_sorted_replicas_query* q,
+                                 const int32_t* brokers /* [n] broker indices, or NULL = brokers 0..n-1 with n == B */,
+                                 int64_t n, int64_t* offsets /* [n + 1] */,
+                                 ccmi_swap_replica* records /* [capacity] */, double* scores /* [capacity] or NULL */,
+                                 int64_t capacity, int64_t* num_records, int64_t* first_invalid /* optional */);
 
 /*
  * Destination-sharded mode (one process per GPU): every rank creates a session on its own device from the same
