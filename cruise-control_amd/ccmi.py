@@ -246,9 +246,32 @@ class SortedReplicasQueryStruct(C.Structure):  # ccmi_sorted_replicas_query, 64 
                 ("topic_excluded", C.POINTER(C.c_uint8)), ("topic_included", C.POINTER(C.c_uint8))]
 
 
+class ExecutionPlanQueryStruct(C.Structure):  # ccmi_execution_plan_query, 64 bytes
+    _fields_ = [("num_strategies", C.c_int32), ("strategies", C.c_int32 * 4), ("reserved", C.c_int32 * 7),
+                ("proposal_rank", C.POINTER(C.c_int32)), ("partition_state", C.POINTER(C.c_uint8))]
+
+
+class PlanTaskStruct(C.Structure):  # ccmi_plan_task, 16 bytes
+    _fields_ = [("partition", C.c_int32), ("num_to_add", C.c_int32), ("data_to_move_mb", C.c_int64)]
+
+
+class PlanSummaryStruct(C.Structure):  # ccmi_plan_summary, 64 bytes
+    _fields_ = [("num_inter_tasks", C.c_int64), ("num_inter_entries", C.c_int64), ("num_intra_tasks", C.c_int64),
+                ("num_leader_tasks", C.c_int64), ("num_brokers_with_tasks", C.c_int64), ("size_overflow", C.c_int64),
+                ("mingled", C.c_int64), ("reserved", C.c_int64)]
+
+
 # CCMI_SEL_* (ReplicaSortFunctionFactory's selection functions) and CCMI_PRIO_* (its priority functions)
 SEL_LEADERS, SEL_FOLLOWERS, SEL_ONLINE, SEL_OFFLINE, SEL_IMMIGRANTS, SEL_IMMIGRANT_OR_OFFLINE = 1, 2, 4, 8, 16, 32
 SORT_PRIORITIES = ("offline", "immigrants")  # index = CCMI_PRIO_*
+# CCMI_STRATEGY_* (index = value; the simple names of the executor/strategy classes) and CCMI_PSTATE_*
+MOVEMENT_STRATEGIES = ("BaseReplicaMovementStrategy", "PrioritizeLargeReplicaMovementStrategy",
+                       "PrioritizeSmallReplicaMovementStrategy", "PostponeUrpReplicaMovementStrategy",
+                       "PrioritizeMinIsrWithOfflineReplicasStrategy",
+                       "PrioritizeOneAboveMinIsrWithOfflineReplicasStrategy")
+(STRATEGY_BASE, STRATEGY_PRIORITIZE_LARGE, STRATEGY_PRIORITIZE_SMALL, STRATEGY_POSTPONE_URP,
+ STRATEGY_PRIORITIZE_MIN_ISR_WITH_OFFLINE, STRATEGY_PRIORITIZE_ONE_ABOVE_MIN_ISR_WITH_OFFLINE) = range(6)
+PSTATE_UNDER_REPLICATED, PSTATE_UNDER_MIN_ISR, PSTATE_AT_MIN_ISR, PSTATE_ONE_ABOVE_MIN_ISR = 1, 2, 4, 8
 
 
 # ----------------------------------------------------------------------------------------------- errors
@@ -288,7 +311,7 @@ EXPORTED_SYMBOLS = (
     "ccmi_session_apply", "ccmi_last_failure_provision",
     "ccmi_compute_cluster_stats", "ccmi_broker_stats", "ccmi_partition_load", "ccmi_action_log_count", "ccmi_action_log_copy", "ccmi_replica_distribution",
     "ccmi_leader_distribution", "ccmi_replica_disks", "ccmi_proposal_count", "ccmi_proposals",
-    "ccmi_proposal_disks", "ccmi_proposal_diff", "ccmi_sorted_replicas", "ccmi_perf", "ccmi_perf_reset", "ccmi_host_prefix_perf", "ccmi_host_cross_perf",
+    "ccmi_proposal_disks", "ccmi_proposal_diff", "ccmi_sorted_replicas", "ccmi_execution_plan", "ccmi_perf", "ccmi_perf_reset", "ccmi_host_prefix_perf", "ccmi_host_cross_perf",
     "ccmi_set_kernel_timing", "ccmi_session_set_shard", "ccmi_rccl_unique_id", "ccmi_session_attach_rccl",
     "ccmi_session_attach_shm", "ccmi_session_attach_shm_job", "ccmi_shard_group_create", "ccmi_shard_group_destroy", "ccmi_session_attach_group",
     "ccmi_topic_broker_set",
@@ -363,6 +386,12 @@ class Library:
             L.ccmi_sorted_replicas.argtypes = [C.c_void_p, C.POINTER(SortedReplicasQueryStruct), C.c_void_p, C.c_int64,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
                                                C.POINTER(C.c_int64)]
+        self.has_execution_plan = hasattr(L, "ccmi_execution_plan")
+        if self.has_execution_plan:
+            L.ccmi_execution_plan.argtypes = [C.c_void_p, C.POINTER(ExecutionPlanQueryStruct),
+                                              C.POINTER(PlanSummaryStruct), C.c_void_p, C.c_int64, C.c_void_p,
+                                              C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                              C.c_void_p, C.c_int64]
         L.ccmi_session_apply.argtypes = [C.c_void_p, C.POINTER(ActionStruct), C.c_int64, C.POINTER(C.c_int64)]
         L.ccmi_last_failure_provision.argtypes = [C.c_void_p, C.POINTER(ProvisionRespStruct)]
         L.ccmi_compute_cluster_stats.argtypes = [C.c_void_p, C.POINTER(ConstraintStruct), C.POINTER(OptionsStruct),
@@ -872,6 +901,97 @@ class ProposalDiff:
         return [int(s.num_inter_broker_replica_movements), int(s.inter_broker_data_to_move_mb),
                 int(s.num_intra_broker_replica_movements), int(s.intra_broker_data_to_move_mb),
                 int(s.num_leadership_movements)]
+
+
+class ExecutionPlan:
+    """What ExecutionTaskPlanner.addExecutionProposals builds from the proposals of the session's current model, as
+    ccmi_execution_plan computed it on the device. `tasks` is a numpy structured array with the fields of
+    PlanTaskStruct, indexed by execution id; `inter[b]` the execution ids of broker b's inter-broker tasks in strategy
+    order; `broker_order` the brokers with such tasks in brokerComparator's initial order; `intra[b]` the partitions of
+    broker b's intra-broker tasks and `leader_tasks` the partitions of the leadership tasks, both in proposal order;
+    `summary` a PlanSummaryStruct. `strategies` (CCMI_STRATEGY_* numbers) and `partition_state` are the query's."""
+
+    def __init__(self, summary: PlanSummaryStruct, tasks, inter, broker_order, intra, leader_tasks, strategies,
+                 partition_state):
+        self.summary = summary
+        self.tasks = tasks
+        self.inter = inter
+        self.broker_order = broker_order
+        self.intra = intra
+        self.leader_tasks = leader_tasks
+        self.strategies = list(strategies)
+        self.partition_state = partition_state
+        # next_round's state: the tasks still filed under each broker, and the brokers of each task
+        self._lists = [[int(t) for t in seg] for seg in inter]
+        self._brokers = {}
+        for b, seg in enumerate(self._lists):
+            for t in seg:
+                self._brokers.setdefault(t, []).append(b)
+
+    def task_key(self, t: int):
+        """Task t's place under the chain as a tuple: the device's order (sizes compared as int64)."""
+        st = int(self.partition_state[int(self.tasks["partition"][t])]) if self.partition_state is not None else 0
+        data, key = int(self.tasks["data_to_move_mb"][t]), []
+        for s in self.strategies:
+            if s == STRATEGY_BASE:
+                break
+            key.append({STRATEGY_PRIORITIZE_LARGE: -data, STRATEGY_PRIORITIZE_SMALL: data,
+                        STRATEGY_POSTPONE_URP: 1 if st & PSTATE_UNDER_REPLICATED else 0,
+                        STRATEGY_PRIORITIZE_MIN_ISR_WITH_OFFLINE:
+                            0 if st & PSTATE_UNDER_MIN_ISR else 1 if st & PSTATE_AT_MIN_ISR else 2,
+                        STRATEGY_PRIORITIZE_ONE_ABOVE_MIN_ISR_WITH_OFFLINE:
+                            0 if st & PSTATE_ONE_ABOVE_MIN_ISR else 1}[s])
+        return tuple(key) + (t,)
+
+    def remaining(self) -> int:
+        """Inter-broker tasks no round has taken yet."""
+        return len(self._brokers)
+
+    def next_round(self, ready_brokers: Dict[int, int], in_progress=(), max_moves: int = 1 << 30) -> List[int]:
+        """ExecutionTaskPlanner.getInterBrokerReplicaMovementTasks (ExecutionTaskPlanner.java:348-439) over the
+        returned lists, on the host: the execution ids of the next executable tasks, which leave the plan.
+        `ready_brokers` maps a broker to its free movement slots and is decremented as the reference decrements it (a
+        broker of a checked task that is missing raises KeyError, where the reference throws a NullPointerException);
+        `in_progress` holds partition indices; `max_moves` caps in-progress plus returned partitions. The source of
+        a task is the broker its proposal's old leader is on; the lists file a task under it and under every
+        destination, and the round treats the two alike, so the brokers of a task are those whose list holds it."""
+        lists, out = self._lists, []
+        busy_parts = set(int(p) for p in in_progress)
+        num_in_progress, involved_parts = len(busy_parts), set()
+
+        def broker_key(b):  # brokerComparator on the lists as they are now
+            return (self.task_key(lists[b][0]), -len(lists[b]), b)
+
+        added, capped = True, False
+        while added and not capped:
+            added = False
+            involved = set()
+            for b in sorted((b for b in range(len(lists)) if lists[b]), key=broker_key):
+                if capped:
+                    break
+                if b in involved:
+                    continue
+                for t in list(lists[b]):
+                    if num_in_progress >= max_moves:
+                        capped = True
+                        break
+                    brokers = self._brokers[t]
+                    if any(x in involved for x in brokers):
+                        continue
+                    part = int(self.tasks["partition"][t])
+                    if all(ready_brokers[x] > 0 for x in brokers) and part not in busy_parts \
+                            and part not in involved_parts:
+                        involved_parts.add(part)
+                        out.append(t)
+                        involved.update(brokers)
+                        for x in brokers:
+                            lists[x].remove(t)
+                            ready_brokers[x] -= 1
+                        del self._brokers[t]
+                        added = True
+                        num_in_progress += 1
+                        break
+        return out
 
 
 class OptimizerResult:
@@ -1703,6 +1823,64 @@ class ClusterModel:
         if with_scores:
             return lists, [scores[offsets[i]:offsets[i + 1]] for i in range(n)]
         return lists
+
+    def execution_plan(self, strategies=(), proposal_rank=None, partition_state=None) -> "ExecutionPlan":
+        """What ExecutionTaskPlanner.addExecutionProposals builds from the proposals proposal_diff() would return now,
+        computed on the device (ccmi_execution_plan), under the assumption that the live cluster still has the
+        session's initial placement with every replica in sync. `strategies` is the ReplicaMovementStrategy chain in
+        application order, at most four of MOVEMENT_STRATEGIES (class names or CCMI_STRATEGY_* numbers; Base is
+        appended when absent); `proposal_rank` ([P] int32) the position of each partition's proposal in the caller's
+        collection (None: partition order); `partition_state` ([P] uint8) the PSTATE_* bits the ISR strategies read
+        (None: no bit set). The buffers are sized by a first call with no room. The session is not changed."""
+        import numpy as np
+
+        if not self.lib.has_execution_plan:
+            self._not_exported("ccmi_execution_plan", "the plan is built on the device only")
+        B, P = self.desc.num_brokers, self.desc.num_partitions
+        chain = [s if isinstance(s, int) else MOVEMENT_STRATEGIES.index(s) for s in strategies]
+        if len(chain) > 4:
+            raise IllegalArgumentException("at most four strategies")
+        q = ExecutionPlanQueryStruct()
+        q.num_strategies = len(chain)
+        for i in range(4):
+            q.strategies[i] = chain[i] if i < len(chain) else -1
+
+        def per_partition(a, dtype, what):
+            a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+            if len(a) != P:
+                raise IllegalArgumentException(f"{what} needs one entry per partition ({P})")
+            return a if P else np.zeros(1, dtype=dtype)
+
+        rank = state = None
+        if proposal_rank is not None:
+            rank = per_partition(proposal_rank, np.int32, "proposal_rank")
+            q.proposal_rank = rank.ctypes.data_as(C.POINTER(C.c_int32))
+        if partition_state is not None:
+            state = per_partition(partition_state, np.uint8, "partition_state")
+            q.partition_state = state.ctypes.data_as(C.POINTER(C.c_uint8))
+        fn = self.lib.lib.ccmi_execution_plan
+        summary = PlanSummaryStruct()
+        inter_off, intra_off = np.zeros(B + 1, dtype=np.int64), np.zeros(B + 1, dtype=np.int64)
+        order = np.full(max(B, 1), -1, dtype=np.int32)
+        self._checked(fn(self.handle, C.byref(q), C.byref(summary), None, 0, inter_off.ctypes.data, None, 0, None,
+                         intra_off.ctypes.data, None, 0, None, 0))  # the sizing call
+        dropped = summary.num_intra_tasks > 0
+        none = bool(summary.mingled)
+        tasks = np.zeros(0 if dropped else summary.num_inter_tasks, dtype=np.dtype(PlanTaskStruct))
+        inter = np.zeros(int(inter_off[B]), dtype=np.int32)
+        intra = np.zeros(int(intra_off[B]), dtype=np.int32)
+        leaders = np.zeros(0 if none else summary.num_leader_tasks, dtype=np.int32)
+
+        def ptr(a):
+            return a.ctypes.data if len(a) else None
+
+        if len(tasks) or len(inter) or len(intra) or len(leaders):
+            self._checked(fn(self.handle, C.byref(q), C.byref(summary), ptr(tasks), len(tasks), inter_off.ctypes.data,
+                             ptr(inter), len(inter), order.ctypes.data if len(inter) else None, intra_off.ctypes.data,
+                             ptr(intra), len(intra), ptr(leaders), len(leaders)))
+        return ExecutionPlan(summary, tasks, [inter[inter_off[b]:inter_off[b + 1]] for b in range(B)],
+                             order[:summary.num_brokers_with_tasks].copy(),
+                             [intra[intra_off[b]:intra_off[b + 1]] for b in range(B)], leaders, chain, state)
 
     def apply(self, actions) -> int:
         """Apply actions decided elsewhere (tuples in the action-log layout: type, partition, source,

@@ -304,6 +304,11 @@ Device::~Device() {
     if (p) (void)hipFree(p);
   if (dSrRecords_) (void)hipFree(dSrRecords_);
   if (dSrScores_) (void)hipFree(dSrScores_);
+  for (void* p : epAllocs_)  // executionPlan (device_accept.cpp)
+    if (p) (void)hipFree(p);
+  for (void* p : {(void*)dEpBuf_[0], (void*)dEpBuf_[1], (void*)dEpTasks_, (void*)dEpInterOut_, (void*)dEpIntraOut_,
+                  (void*)dEpLeaderOut_})
+    if (p) (void)hipFree(p);
   if (hStage_) (void)hipHostFree(hStage_);
   if (hResult_) (void)hipHostFree(hResult_);
   if (ev0_) (void)hipEventDestroy(EV0);

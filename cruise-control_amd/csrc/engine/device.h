@@ -26,6 +26,8 @@ struct ccmi_partition_load_record;
 struct ccmi_swap_replica;
 struct ccmi_proposal_record;
 struct ccmi_proposal_summary;
+struct ccmi_plan_task;
+struct ccmi_plan_summary;
 
 namespace ccmi {
 
@@ -337,6 +339,17 @@ class Device {
                       const uint8_t* topicIncluded, int64_t* offsets, ccmi_swap_replica* records, double* scores,
                       int64_t capacity, int64_t* numRecords);
 
+  // K16 (kernels/execution_plan.hip, device_accept.cpp): what ExecutionTaskPlanner.addExecutionProposals builds from
+  // the proposals of K14; needs uploadInitialPlacement. The pending row updates and the pending chain loads
+  // (syncChainLoads) reach the tables first; curDisks as proposalDiff's; rank[P] and state[P] may each be null. summary,
+  // interOffsets[B + 1] and intraOffsets[B + 1] are always written; the other arrays only when every list fits its
+  // capacity. One stream sync for the sums and offsets, one more for the lists. Counts into perf.statsLaunches /
+  // statsKernelMs / statsBytes. Not in the test emulation.
+  void executionPlan(const EpQuery& q, const int32_t* curDisks, const int32_t* rank, const uint8_t* state,
+                     ccmi_plan_summary* summary, ccmi_plan_task* tasks, int64_t taskCap, int64_t* interOffsets,
+                     int32_t* interEntries, int64_t interCap, int32_t* brokerOrder, int64_t* intraOffsets,
+                     int32_t* intraEntries, int64_t intraCap, int32_t* leaderTasks, int64_t leaderCap);
+
   // Disks (JBOD): the static disk / replica tables once per session; setDiskUtil whenever the host changed a disk's
   // utilization; intraRun = one intra-broker goal (K6); statsDisks = the disk part of ClusterModelStats.
   void uploadDisks(int D, const int32_t* bDiskOff, const int32_t* bDisks, const double* dCap, const uint8_t* dAlive,
@@ -522,6 +535,21 @@ class Device {
   size_t srOutCap_ = 0;
   std::vector<void*> srAllocs_;
   std::vector<unsigned long long> srHost_;
+  // executionPlan: the rows and execution ids [P], the call's rank [P], state [P] and current disks [R], the tile
+  // counts [2][tiles + 1], the broker counts and cursors [2 B], the sums, {total, longest, offsets} of both lists and the
+  // two one-segment offsets [2 (B + 3) + 4]; the entry buffers and the output arrays grow to the largest call so far
+  EpRow* dEpRows_ = nullptr;
+  int32_t *dEpIdOf_ = nullptr, *dEpRank_ = nullptr, *dEpCurDisks_ = nullptr, *dEpOrder_ = nullptr;
+  uint8_t* dEpPState_ = nullptr;
+  uint32_t *dEpTiles_ = nullptr, *dEpCounts_ = nullptr, *dEpCursors_ = nullptr;
+  EpSums* dEpSums_ = nullptr;
+  unsigned long long* dEpState_ = nullptr;
+  EpEntry* dEpBuf_[2] = {nullptr, nullptr};
+  ccmi_plan_task* dEpTasks_ = nullptr;
+  int32_t *dEpInterOut_ = nullptr, *dEpIntraOut_ = nullptr, *dEpLeaderOut_ = nullptr;
+  size_t epBufCap_ = 0, epTaskCap_ = 0, epInterCap_ = 0, epIntraCap_ = 0, epLeaderCap_ = 0;
+  std::vector<void*> epAllocs_;
+  std::vector<unsigned long long> epHost_;
   // the pending chain loads (lrows / srows) go to the device's Java loads and slot order outside a chain
   void syncChainLoads();
   int32_t* dRackRes_ = nullptr;  // rackRowsGroups results (+ the evaluated-candidate counter after them)

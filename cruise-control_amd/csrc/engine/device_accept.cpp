@@ -3,7 +3,8 @@
 // share one chunk protocol (Device::acceptChunk); and Device::brokerStats, the launcher of K12
 // (kernels/broker_stats.hip), Device::partitionLoad, the launcher of K13 (kernels/partition_load.hip), and
 // Device::proposalDiff, the launcher of K14 (kernels/proposal_diff.hip), and Device::sortedReplicas, the launcher of K15
-// (kernels/sorted_replicas.hip), which share its scope and timing. A translation unit of its own, linked into libccmi.so
+// (kernels/sorted_replicas.hip), and Device::executionPlan, the launcher of K16 (kernels/execution_plan.hip), which
+// share its scope and timing. A translation unit of its own, linked into libccmi.so
 // only: the test emulation of Device has none of these kernels.
 #include <hip/hip_runtime.h>
 
@@ -46,6 +47,16 @@ hipError_t launchSortedReplicasFill(const SrTables& T, const SrQuery& q, int n, 
                                     const int32_t* segOf, uint32_t* cursor, const unsigned long long* state,
                                     long long total, long long maxLen, SrEntry* bufA, SrEntry* bufB,
                                     ccmi_swap_replica* records, double* scores, int* launches, hipStream_t stream);
+hipError_t launchExecutionPlanCount(const EpTables& T, int tiles, EpRow* rows, uint32_t* tileInter,
+                                    uint32_t* tileLeader, uint32_t* counts, uint32_t* cursors, EpSums* sums,
+                                    unsigned long long* state, int* launches, hipStream_t stream);
+hipError_t launchExecutionPlanFill(const EpTables& T, const EpQuery& q, int tiles, const EpRow* rows,
+                                   const uint32_t* tileInter, const uint32_t* tileLeader, uint32_t* cursors,
+                                   const unsigned long long* state, long long numInter, long long numLeader,
+                                   long long interTotal, long long interMax, long long intraTotal, long long intraMax,
+                                   EpEntry* bufA, EpEntry* bufB, int32_t* idOf, ccmi_plan_task* tasks, int32_t* interOut,
+                                   int32_t* order, int32_t* intraOut, int32_t* leaderOut, int* launches,
+                                   hipStream_t stream);
 
 namespace {
 constexpr double kAcceptWaitSeconds = 120.0;
@@ -582,6 +593,167 @@ void Device::sortedReplicas(const SrQuery& q, const int32_t* seg, int n, const u
     // pass, the gather's entry and replica words in and a record (and a score) out
     perf.statsBytes += (int64_t)R_ * 12 + total * (int64_t)(sizeof(SrEntry) * (4 + 2 * (fill - 3)) + 16 + 8 + (scores ? 8 : 0));
   }
+  perf.statsLaunches += launches;
+}
+
+void Device::executionPlan(const EpQuery& q, const int32_t* curDisks, const int32_t* rank, const uint8_t* state,
+                           ccmi_plan_summary* summary, ccmi_plan_task* tasks, int64_t taskCap, int64_t* interOffsets,
+                           int32_t* interEntries, int64_t interCap, int32_t* brokerOrder, int64_t* intraOffsets,
+                           int32_t* intraEntries, int64_t intraCap, int32_t* leaderTasks, int64_t leaderCap) {
+  PlainLaunch call(*this);
+  if (!dPdInitDist_) throw std::logic_error("executionPlan before uploadInitialPlacement");
+  if (!summary || !interOffsets || !intraOffsets || taskCap < 0 || interCap < 0 || intraCap < 0 || leaderCap < 0 ||
+      (D_ > 0) != (curDisks != nullptr) || P_ < 1 || B_ < 1)
+    throw std::logic_error("executionPlan: arguments");
+  const hipStream_t st = (hipStream_t)st_;
+  const int tiles = (P_ + kPdTile - 1) / kPdTile;
+  const size_t stateWords = 2 * ((size_t)B_ + 3) + 4;
+  if (!dEpSums_) {  // first use
+    auto get = [&](auto** d, size_t n, const char* what) {
+      hipCheck(hipMalloc((void**)d, std::max<size_t>(1, n) * sizeof(**d)), what);
+      epAllocs_.push_back(*d);
+    };
+    get(&dEpRows_, (size_t)P_, "hipMalloc plan rows");
+    get(&dEpIdOf_, (size_t)P_, "hipMalloc execution ids");
+    get(&dEpRank_, (size_t)P_, "hipMalloc proposal ranks");
+    get(&dEpPState_, (size_t)P_, "hipMalloc partition states");
+    if (D_ > 0) get(&dEpCurDisks_, (size_t)R_, "hipMalloc current disks");
+    get(&dEpOrder_, (size_t)B_, "hipMalloc broker order");
+    get(&dEpTiles_, 2 * ((size_t)tiles + 1), "hipMalloc plan tile counts");
+    get(&dEpCounts_, 2 * (size_t)B_, "hipMalloc plan broker counts");
+    get(&dEpCursors_, 2 * (size_t)B_, "hipMalloc plan cursors");
+    get(&dEpState_, stateWords, "hipMalloc plan offsets");
+    get(&dEpSums_, 1, "hipMalloc plan sums");  // last: marks the first use done
+  }
+  // the device's tables current: the pending row updates (prep) and the pending slot orders and leaders (sync_loads)
+  syncChainLoads();
+  if (curDisks)
+    hipCheck(hipMemcpyAsync(dEpCurDisks_, curDisks, (size_t)R_ * sizeof(int32_t), hipMemcpyHostToDevice, st),
+             "upload current disks");
+  if (rank)
+    hipCheck(hipMemcpyAsync(dEpRank_, rank, (size_t)P_ * sizeof(int32_t), hipMemcpyHostToDevice, st),
+             "upload proposal ranks");
+  if (state)
+    hipCheck(hipMemcpyAsync(dEpPState_, state, (size_t)P_, hipMemcpyHostToDevice, st), "upload partition states");
+  EpTables T;
+  T.pd.parts = parts_;
+  T.pd.replicas = replicas_;
+  T.pd.pOff = dPOff_;
+  T.pd.pSlots = dPSlots_;
+  T.pd.pLeader = dPLeader_;
+  T.pd.initDist = dPdInitDist_;
+  T.pd.initLeaders = dPdInitLeaders_;
+  T.pd.initDisks = curDisks ? dPdInitDisks_ : nullptr;
+  T.pd.initLeaderDisks = curDisks ? dPdInitLeaderDisks_ : nullptr;
+  T.pd.curDisks = curDisks ? dEpCurDisks_ : nullptr;
+  T.pd.R = R_;
+  T.pd.P = P_;
+  T.rank = rank ? dEpRank_ : nullptr;
+  T.state = state ? dEpPState_ : nullptr;
+  T.B = B_;
+  uint32_t* tileInter = dEpTiles_;
+  uint32_t* tileLeader = dEpTiles_ + tiles + 1;
+  int launches = 0;
+  timedLaunch([&] {
+    hipCheck(launchExecutionPlanCount(T, tiles, dEpRows_, tileInter, tileLeader, dEpCounts_, dEpCursors_, dEpSums_,
+                                      dEpState_, &launches, st),
+             "execution_plan classify");
+  });
+  // one small read-back: the sums, and both lists' totals, longest segments and offsets, which the caller gets whatever
+  // the capacities
+  EpSums sums;
+  epHost_.resize(stateWords);
+  hipCheck(hipMemcpyAsync(&sums, dEpSums_, sizeof(sums), hipMemcpyDeviceToHost, st), "D2H plan sums");
+  hipCheck(hipMemcpyAsync(epHost_.data(), dEpState_, stateWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st),
+           "D2H plan offsets");
+  streamWait("execution_plan classify", kAcceptWaitSeconds);
+  perf.syncs++;
+  addKernelMs(perf.statsKernelMs);
+  const unsigned long long* hInter = epHost_.data();
+  const unsigned long long* hIntra = epHost_.data() + (size_t)B_ + 3;
+  const int64_t interTasks = (int64_t)sums.v[0], intraTasks = (int64_t)sums.v[2], leaderAll = (int64_t)sums.v[3];
+  const bool dropped = intraTasks > 0;                // maybeDropReplicaSwapTasks
+  const bool mingled = dropped && sums.v[5] > 0;      // sanityCheckExecutionTasks throws
+  const int64_t interTotal = mingled ? 0 : (int64_t)hInter[0], interMax = mingled ? 0 : (int64_t)hInter[1];
+  const int64_t intraTotal = mingled ? 0 : (int64_t)hIntra[0], intraMax = mingled ? 0 : (int64_t)hIntra[1];
+  const int64_t numTasks = dropped ? 0 : interTasks, numLeader = mingled ? 0 : leaderAll;
+  if (interTasks > P_ || leaderAll > P_ || (int64_t)hIntra[0] != intraTasks || interMax > interTotal ||
+      intraMax > intraTotal || interTotal > 9 * (int64_t)P_ || intraTotal > (int64_t)R_ ||
+      hInter[0] != (dropped ? 0ull : sums.v[1]))
+    throw std::runtime_error("device execution_plan: impossible counts");
+  int64_t withTasks = 0;
+  for (int b = 0; b <= B_; ++b) {
+    interOffsets[b] = mingled ? 0 : (int64_t)hInter[2 + b];
+    intraOffsets[b] = mingled ? 0 : (int64_t)hIntra[2 + b];
+    if (b > 0 && interOffsets[b] > interOffsets[b - 1]) withTasks++;
+  }
+  *summary = ccmi_plan_summary{};
+  summary->num_inter_tasks = interTasks;
+  summary->num_inter_entries = interTotal;
+  summary->num_intra_tasks = intraTasks;
+  summary->num_leader_tasks = leaderAll;
+  summary->num_brokers_with_tasks = withTasks;
+  summary->size_overflow = sums.v[4] > 0 ? 1 : 0;
+  summary->mingled = mingled ? 1 : 0;
+  // per partition its record, offsets, leader id, the leader's replica record words, the initial brokers and leader (and
+  // the disks), a row out; per broker two counts, two cursors and two offsets
+  perf.statsBytes += (int64_t)P_ * (int64_t)(sizeof(PartitionRec) + 8 + 4 + 32 + 4 + (curDisks ? 4 : 0) + sizeof(EpRow)) +
+                     (int64_t)R_ * 4 * (curDisks ? 4 : 1) + (int64_t)tiles * 16 + (int64_t)B_ * 32;
+  const int64_t entries = numTasks + numLeader + interTotal + intraTotal;
+  const bool fits = numTasks <= taskCap && interTotal <= interCap && intraTotal <= intraCap && numLeader <= leaderCap;
+  if (entries > 0 && fits) {
+    if ((numTasks > 0 && !tasks) || (interTotal > 0 && (!interEntries || !brokerOrder)) ||
+        (intraTotal > 0 && !intraEntries) || (numLeader > 0 && !leaderTasks))
+      throw std::logic_error("executionPlan: no room for the lists");
+    auto grow = [&](auto** d, size_t& cap, size_t need, size_t round, const char* what) {
+      if (need <= cap) return;
+      if (*d) hipCheck(hipFree(*d), "hipFree");
+      *d = nullptr;
+      cap = 0;
+      const size_t room = (need + round - 1) / round * round;  // whole 16-byte stores
+      hipCheck(hipMalloc((void**)d, room * sizeof(**d)), what);
+      cap = need;
+    };
+    if ((size_t)entries > epBufCap_) {  // both buffers: a merge pass may come with any call
+      size_t cap0 = 0;
+      grow(&dEpBuf_[0], cap0, (size_t)entries, 1, "hipMalloc plan entries");
+      cap0 = 0;
+      grow(&dEpBuf_[1], cap0, (size_t)entries, 1, "hipMalloc plan merge buffer");
+      epBufCap_ = (size_t)entries;
+    }
+    grow(&dEpTasks_, epTaskCap_, (size_t)numTasks, 1, "hipMalloc plan tasks");
+    grow(&dEpInterOut_, epInterCap_, (size_t)interTotal, 4, "hipMalloc plan inter entries");
+    grow(&dEpIntraOut_, epIntraCap_, (size_t)intraTotal, 4, "hipMalloc plan intra entries");
+    grow(&dEpLeaderOut_, epLeaderCap_, (size_t)numLeader, 4, "hipMalloc plan leader tasks");
+    int fill = 0;
+    timedLaunch([&] {
+      hipCheck(launchExecutionPlanFill(T, q, tiles, dEpRows_, tileInter, tileLeader, dEpCursors_, dEpState_, numTasks,
+                                       numLeader, interTotal, interMax, intraTotal, intraMax, dEpBuf_[0], dEpBuf_[1],
+                                       dEpIdOf_, dEpTasks_, dEpInterOut_, dEpOrder_, dEpIntraOut_, dEpLeaderOut_, &fill,
+                                       st),
+               "execution_plan fill");
+    });
+    auto back = [&](void* h, const void* d, size_t bytes, const char* what) {
+      if (bytes) hipCheck(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, st), what);
+    };
+    back(tasks, dEpTasks_, (size_t)numTasks * sizeof(ccmi_plan_task), "D2H plan tasks");
+    back(interEntries, dEpInterOut_, (size_t)interTotal * sizeof(int32_t), "D2H plan inter entries");
+    if (interTotal > 0) back(brokerOrder, dEpOrder_, (size_t)B_ * sizeof(int32_t), "D2H broker order");
+    back(intraEntries, dEpIntraOut_, (size_t)intraTotal * sizeof(int32_t), "D2H plan intra entries");
+    back(leaderTasks, dEpLeaderOut_, (size_t)numLeader * sizeof(int32_t), "D2H plan leader tasks");
+    streamWait("execution_plan fill", kAcceptWaitSeconds);
+    perf.syncs++;
+    addKernelMs(perf.statsKernelMs);
+    launches += fill;
+    // per partition a row in (number, scatter); per task partition the proposal's tables again; per entry a write, the
+    // sorts' and merge passes' reads and writes, the gather's read and a word out
+    perf.statsBytes += (int64_t)P_ * 2 * (int64_t)sizeof(EpRow) +
+                       (numTasks + intraTotal) * (int64_t)(sizeof(PartitionRec) + 64) +
+                       entries * (int64_t)(sizeof(EpEntry) * (4 + 2 * std::max(0, fill - 8)) + 4) +
+                       numTasks * (int64_t)sizeof(ccmi_plan_task);
+  }
+  if (interTotal == 0 && fits && brokerOrder)  // no broker has tasks: the whole order is "none"
+    std::fill(brokerOrder, brokerOrder + B_, -1);
   perf.statsLaunches += launches;
 }
 

@@ -347,6 +347,38 @@ struct SrTables {
   int32_t B, R, P, T, W;
 };
 
+// ccmi_execution_plan (kernels/execution_plan.hip): what ExecutionTaskPlanner.addExecutionProposals builds from the
+// proposals of K14. EpRow: one partition's tasks as the classify kernel leaves them. EpEntry: one sort entry, a 128-bit
+// key compared hi then lo; every list's payload is the key's own low bits (an execution id or a partition index), and no
+// two entries of a segment share a key. EpQuery: the chain as the kernels apply it: the strategies before BASE, a second
+// size strategy dropped (it never decides after the first). EpSums: the device sums behind ccmi_plan_summary.
+constexpr int kEpSortTile = 4096;  // entries one workgroup sorts in LDS (64 KB), as kSrSortTile
+enum : int32_t { EP_INTER = 1, EP_LEADER = 2 };  // EpRow.flags bits 0 / 1; bits 8..11 num_to_add, 12..15 between disks
+struct alignas(16) EpRow {
+  int32_t flags;
+  int32_t src;   // the old leader's broker: the broker an inter-broker task is filed under besides its destinations
+  int64_t data;  // ExecutionProposal.dataToMoveInMB
+};
+struct alignas(16) EpEntry {
+  uint64_t lo, hi;
+};
+static_assert(sizeof(EpRow) == 16 && sizeof(EpEntry) == 16, "one 16-byte access each");
+struct EpQuery {
+  int32_t n;         // strategies that can decide before the execution id
+  int32_t strat[4];  // CCMI_STRATEGY_* (never BASE)
+};
+struct EpSums {
+  // inter-broker tasks, their list entries, intra-broker tasks, leadership tasks, inter-broker tasks whose data exceeds
+  // INT32_MAX, inter-broker tasks with replicas to add
+  unsigned long long v[8];
+};
+struct EpTables {
+  PdTables pd;
+  const int32_t* rank;   // [P] proposal_rank or null
+  const uint8_t* state;  // [P] partition_state or null
+  int32_t B;
+};
+
 struct UpdateList {
   const BrokerRow* brows;
   const ReplicaRow* rrows;

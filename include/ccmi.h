@@ -36,6 +36,9 @@
  *   ccmi_sorted_replicas       <- SortedReplicas.sortedReplicas  model/SortedReplicas.java:75-114
  *                                 analyzer/AnalyzerUtils.java:63-93, analyzer/OptimizerResult.java:258-278 (the proposals
  *                                 and the five movement numbers of the current model, diffed on the device)
+ *   ccmi_execution_plan        <- ExecutionTaskPlanner.addExecutionProposals  executor/ExecutionTaskPlanner.java:137-273,
+ *                                 brokerComparator :518-539, strategy/AbstractReplicaMovementStrategy.java:28-85 (the
+ *                                 tasks, their ids, the per-broker task sets in strategy order, the broker order)
  *   ccmi_random_cluster        <- test fixture RandomCluster.generate+populate
  *                                 (src/test/java/.../model/RandomCluster.java:53-455)
  *
@@ -804,6 +807,108 @@ ccmi_status ccmi_sorted_replicas(ccmi_session* s, const ccmi_sorted_replicas_que
                                  int64_t n, int64_t* offsets /* [n + 1] */,
                                  ccmi_swap_replica* records /* [capacity] */, double* scores /* [capacity] or NULL */,
                                  int64_t capacity, int64_t* num_records, int64_t* first_invalid /* optional */);
+
+/* The ReplicaMovementStrategy classes of executor/strategy/ and the per-partition state their comparators read. */
+enum { CCMI_STRATEGY_BASE = 0,                /* BaseReplicaMovementStrategy: the execution id */
+       CCMI_STRATEGY_PRIORITIZE_LARGE = 1,    /* PrioritizeLargeReplicaMovementStrategy: dataToMoveInMB descending */
+       CCMI_STRATEGY_PRIORITIZE_SMALL = 2,    /* PrioritizeSmallReplicaMovementStrategy: dataToMoveInMB ascending */
+       CCMI_STRATEGY_POSTPONE_URP = 3,        /* PostponeUrpReplicaMovementStrategy */
+       CCMI_STRATEGY_PRIORITIZE_MIN_ISR_WITH_OFFLINE = 4,           /* PrioritizeMinIsrWithOfflineReplicasStrategy */
+       CCMI_STRATEGY_PRIORITIZE_ONE_ABOVE_MIN_ISR_WITH_OFFLINE = 5, /* PrioritizeOneAboveMinIsrWithOfflineReplicasStrategy */
+       CCMI_NUM_STRATEGIES = 6 };
+enum { CCMI_PSTATE_UNDER_REPLICATED = 1,      /* ExecutionUtils.isPartitionUnderReplicated */
+       CCMI_PSTATE_UNDER_MIN_ISR = 2,         /* in populateMinIsrState's underMinIsr set (with offline replicas) */
+       CCMI_PSTATE_AT_MIN_ISR = 4,            /* in its atMinIsr set */
+       CCMI_PSTATE_ONE_ABOVE_MIN_ISR = 8 };   /* in its oneAboveMinIsr set */
+/* What the caller of ExecutionTaskPlanner.addExecutionProposals brings besides the proposals. 64 bytes. */
+typedef struct ccmi_execution_plan_query {
+  int32_t num_strategies;         /* 0..4 */
+  int32_t strategies[4];          /* CCMI_STRATEGY_* in application order (ReplicaMovementStrategy.chain); unused = -1 */
+  int32_t reserved[7];            /* 0 */
+  const int32_t* proposal_rank;   /* [P] or NULL: the position of a partition's proposal in the caller's collection */
+  const uint8_t* partition_state; /* [P] or NULL: OR of CCMI_PSTATE_* per partition; NULL = no flag set */
+} ccmi_execution_plan_query;
+/* One inter-broker ExecutionTask; its execution id is its position in the task table. 16 bytes. */
+typedef struct ccmi_plan_task {
+  int32_t partition;        /* partition index (desc order) */
+  int32_t num_to_add;       /* |replicasToAdd|: the task's destination brokers */
+  int64_t data_to_move_mb;  /* ExecutionProposal.dataToMoveInMB (:242-244): (num_to_add + num_between_disks) * size */
+} ccmi_plan_task;
+/* 64 bytes. */
+typedef struct ccmi_plan_summary {
+  int64_t num_inter_tasks;         /* inter-broker tasks created, before maybeDropReplicaSwapTasks */
+  int64_t num_inter_entries;       /* entries of inter_entries: inter_offsets[B]; 0 after the drop */
+  int64_t num_intra_tasks;         /* intra-broker tasks created: entries of intra_entries, intra_offsets[B], unless mingled */
+  int64_t num_leader_tasks;        /* leadership tasks created: entries of leader_tasks unless mingled */
+  int64_t num_brokers_with_tasks;  /* brokers with a non-empty inter-broker list: the valid prefix of broker_order */
+  int64_t size_overflow;           /* 1: some inter-broker task's data_to_move_mb exceeds INT32_MAX (see below) */
+  int64_t mingled;                 /* 1: the reference throws IllegalStateException (see below); every list is empty */
+  int64_t reserved;                /* 0 */
+} ccmi_plan_summary;
+/* Additive at ABI v13 (the capability flag is the presence of the symbol). What ExecutionTaskPlanner.addExecutionProposals
+ * (executor/ExecutionTaskPlanner.java:137-273) builds from the proposals ccmi_proposal_diff would return now, computed on
+ * the device from the resident tables: the tasks, their execution ids, the per-broker task sets in strategy order and the
+ * first round's broker order (brokerComparator, :518-539).
+ * Assumption: the live Kafka cluster still has the session's initial placement, leaders and logdirs, and every replica is
+ * in sync: the state in which a freshly computed proposal set reaches the executor. The planner's three cluster reads are
+ * answered from it: isInterBrokerMovementCompleted (ExecutionProposal.java:120-122) is "new_replicas equals old_replicas
+ * as a broker sequence", the current logdir of a replica is its old disk, and the current leader is old_leader.
+ * Inter-broker tasks: a proposal whose new_replicas differs from old_replicas as a broker sequence. So a leadership-only
+ * proposal has one (data_to_move_mb 0, no destination), a disk-only proposal none.
+ * Execution ids follow the iteration order of the caller's Collection<ExecutionProposal>, which the device does not hold:
+ * tasks are numbered in ascending (proposal_rank[p], partition index), a total order whatever the array holds;
+ * proposal_rank == NULL is the partition index. Inter-broker tasks get ids 0..num_inter_tasks-1 (they are created first,
+ * :141); tasks[id] describes task id. The ids of intra-broker and leadership tasks are not reported: within a proposal
+ * they follow a HashMap's order and no output order depends on them.
+ * Inter-broker lists: task t is filed under old_leader (the reference files it under the old leader only, not under every
+ * broker that loses a replica: AbstractReplicaMovementStrategy.java:69) and under every broker of replicasToAdd (:76).
+ * Segment b, inter_entries[inter_offsets[b], inter_offsets[b + 1]), holds the execution ids of broker b's TreeSet in
+ * iteration order under the chain q->strategies; BaseReplicaMovementStrategy is appended when the chain lacks it
+ * (chainBaseReplicaMovementStrategyIfAbsent), so the order is total, and a strategy named after BASE never decides.
+ *   BASE: the execution id. PRIORITIZE_LARGE / PRIORITIZE_SMALL: data_to_move_mb descending / ascending.
+ *   POSTPONE_URP: a partition without CCMI_PSTATE_UNDER_REPLICATED first.
+ *   PRIORITIZE_MIN_ISR_WITH_OFFLINE: CCMI_PSTATE_UNDER_MIN_ISR first, then CCMI_PSTATE_AT_MIN_ISR without it, then the rest.
+ *   PRIORITIZE_ONE_ABOVE_MIN_ISR_WITH_OFFLINE: CCMI_PSTATE_ONE_ABOVE_MIN_ISR first.
+ * The session does not hold the live ISR state; the caller evaluates it once per partition into partition_state. Naming
+ * one of the three with partition_state == NULL is allowed: it never decides. A partition missing from the cluster
+ * metadata is outside the contract.
+ * Size overflow: the Java size comparators are (int)(d2 - d1) on longs, a consistent order exactly when every
+ * data_to_move_mb fits int32. The device always orders by the int64 value and sets size_overflow when some inter-broker
+ * task's value exceeds INT32_MAX; the caller decides what to do then.
+ * broker_order[0, num_brokers_with_tasks) lists the brokers with a non-empty inter-broker list in brokerComparator's
+ * initial order: the chain applied to each broker's first task, then the longer list, then the smaller broker index
+ * (index order is id order); the rest of broker_order[B] is -1.
+ * Intra-broker tasks: one per (proposal, broker) of replicasToMoveBetweenDisksByBroker. Segment b of intra_entries holds
+ * the partition indices of broker b's tasks in execution order (ExecutionTask.compareTo), which is proposal order: a
+ * proposal has at most one such task per broker.
+ * Leadership tasks: a proposal with hasLeaderAction whose old_leader is not new_replicas[0] by broker (:262-264; a leader
+ * that only changed disk gets none). leader_tasks holds their partition indices in proposal order.
+ * Drop and throw: when any intra-broker task exists the inter-broker lists, tasks and broker_order are empty
+ * (maybeDropReplicaSwapTasks, :168-173); num_inter_tasks keeps the count before the drop. If in that case some
+ * inter-broker task has num_to_add > 0 the reference throws IllegalStateException (sanityCheckExecutionTasks, :152-160):
+ * mingled = 1, every list is empty (the intra-broker and leadership ones too) and the status is CCMI_OK.
+ * Round selection (getInterBrokerReplicaMovementTasks, :348-439) is serial and depends on live concurrency state: it
+ * stays with the caller, over these lists.
+ * Capacities: summary, inter_offsets[B + 1] and intra_offsets[B + 1] are always written. tasks, inter_entries,
+ * broker_order, intra_entries and leader_tasks are written only when every one of them fits: the tasks that survive the
+ * drop <= task_capacity, num_inter_entries <= inter_capacity, num_intra_tasks <= intra_capacity and num_leader_tasks <=
+ * leader_capacity; otherwise none is touched and the status is still CCMI_OK. All capacities 0 with NULL arrays is the
+ * sizing call.
+ * The session is not changed. Valid on a fresh session (empty lists, a zero summary), after any optimization and after
+ * ccmi_session_apply with nothing in between (the pending rows, slot orders and leaders are sent first; a model with disks
+ * sends its current disks along, as ccmi_proposal_diff). A sharded session answers locally. The launches count into
+ * stats_launches, stats_bytes and stats_kernel_ms of ccmi_perf_counters, as ccmi_broker_stats.
+ * Errors, all before any launch: CCMI_E_INVALID for a NULL s, q, summary, inter_offsets or intra_offsets, a negative
+ * capacity, num_strategies outside 0..4, an unknown strategy or one named twice, an array that is NULL with a capacity
+ * above 0 (its data could fit), and a NULL broker_order with inter_capacity > 0. CCMI_E_DEVICE for a device failure; on
+ * error the outputs are unspecified. */
+ccmi_status ccmi_execution_plan(ccmi_session* s, const ccmi_execution_plan_query* q, ccmi_plan_summary* summary,
+                                ccmi_plan_task* tasks /* [task_capacity] */, int64_t task_capacity,
+                                int64_t* inter_offsets /* [B + 1] */, int32_t* inter_entries /* [inter_capacity] */,
+                                int64_t inter_capacity, int32_t* broker_order /* [B] */,
+                                int64_t* intra_offsets /* [B + 1] */, int32_t* intra_entries /* [intra_capacity] */,
+                                int64_t intra_capacity, int32_t* leader_tasks /* [leader_capacity] */,
+                                int64_t leader_capacity);
 
 /*
  * Destination-sharded mode (one process per GPU): every rank creates a session on its own device from the same
