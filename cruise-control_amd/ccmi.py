@@ -54,6 +54,17 @@ GOAL_KINDS: Dict[str, int] = {
     "KafkaAssignerDiskUsageDistributionGoal": 23,
 }
 GOAL_NAMES = {v: k for k, v in GOAL_KINDS.items()}
+# new IntraBrokerDiskCapacityGoal(true), the goal of RemoveDisksRunnable (:65-67): goal kind 24 of the library. It is
+# the same class, so Goal.name() stays IntraBrokerDiskCapacityGoal and GOAL_KINDS (simple class name -> kind) has no
+# entry of its own; goals_from_names and the by-name acceptance calls know it by this spelling.
+REMOVE_DISKS_GOAL = "IntraBrokerDiskCapacityGoal(true)"
+REMOVE_DISKS_GOAL_KIND = 24
+GOAL_NAMES[REMOVE_DISKS_GOAL_KIND] = "IntraBrokerDiskCapacityGoal"
+
+
+def goal_kind(name: str) -> int:
+    """The library's goal kind of a goal name: a simple class name, or REMOVE_DISKS_GOAL."""
+    return REMOVE_DISKS_GOAL_KIND if name == REMOVE_DISKS_GOAL else GOAL_KINDS[name]
 # default.goals in priority order (config/constants/AnalyzerConfig.java:352-367, TestConstants.DEFAULT_GOALS_VALUES)
 DEFAULT_GOALS = ("RackAwareGoal", "MinTopicLeadersPerBrokerGoal", "ReplicaCapacityGoal", "DiskCapacityGoal",
                  "NetworkInboundCapacityGoal", "NetworkOutboundCapacityGoal", "CpuCapacityGoal",
@@ -308,7 +319,7 @@ EXPORTED_SYMBOLS = (
     "ccmi_random_cluster", "ccmi_cluster_buffers_desc", "ccmi_cluster_buffers_free", "ccmi_session_create",
     "ccmi_session_destroy", "ccmi_optimizations", "ccmi_goal_optimize", "ccmi_action_acceptance",
     "ccmi_action_acceptance_by_kind", "ccmi_actions_acceptance", "ccmi_moves_acceptance_mask", "ccmi_swaps_acceptance_grid",
-    "ccmi_session_apply", "ccmi_last_failure_provision",
+    "ccmi_session_apply", "ccmi_session_mark_disks_for_removal", "ccmi_last_failure_provision",
     "ccmi_compute_cluster_stats", "ccmi_broker_stats", "ccmi_partition_load", "ccmi_action_log_count", "ccmi_action_log_copy", "ccmi_replica_distribution",
     "ccmi_leader_distribution", "ccmi_replica_disks", "ccmi_proposal_count", "ccmi_proposals",
     "ccmi_proposal_disks", "ccmi_proposal_diff", "ccmi_sorted_replicas", "ccmi_execution_plan", "ccmi_perf", "ccmi_perf_reset", "ccmi_host_prefix_perf", "ccmi_host_cross_perf",
@@ -393,6 +404,11 @@ class Library:
                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                               C.c_void_p, C.c_int64]
         L.ccmi_session_apply.argtypes = [C.c_void_p, C.POINTER(ActionStruct), C.c_int64, C.POINTER(C.c_int64)]
+        # additive at ABI v13: the symbol's presence is the capability flag (also of goal kind 24)
+        self.has_remove_disks = hasattr(L, "ccmi_session_mark_disks_for_removal")
+        if self.has_remove_disks:
+            L.ccmi_session_mark_disks_for_removal.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_double,
+                                                              C.POINTER(C.c_int32)]
         L.ccmi_last_failure_provision.argtypes = [C.c_void_p, C.POINTER(ProvisionRespStruct)]
         L.ccmi_compute_cluster_stats.argtypes = [C.c_void_p, C.POINTER(ConstraintStruct), C.POINTER(OptionsStruct),
                                                  C.POINTER(StatsStruct)]
@@ -633,6 +649,24 @@ class Goal:
 
 for _n in GOAL_KINDS:
     globals()[_n] = type(_n, (Goal,), {})
+
+
+class IntraBrokerDiskCapacityGoalEmptyDisks(Goal):
+    """new IntraBrokerDiskCapacityGoal(true) (IntraBrokerDiskCapacityGoal.java:61-63): also empties zero-capacity
+    disks. goals_from_names([REMOVE_DISKS_GOAL]) builds it; name() is IntraBrokerDiskCapacityGoal."""
+
+    def __init__(self, constraint: Optional[BalancingConstraint] = None):
+        super().__init__("IntraBrokerDiskCapacityGoal", constraint)
+
+    @property
+    def kind(self) -> int:
+        return REMOVE_DISKS_GOAL_KIND
+
+    def __repr__(self) -> str:
+        return REMOVE_DISKS_GOAL
+
+
+globals()[REMOVE_DISKS_GOAL] = IntraBrokerDiskCapacityGoalEmptyDisks
 
 
 # ----------------------------------------------------------------------------------------------- results
@@ -1544,7 +1578,7 @@ class ClusterModel:
         a = ActionStruct(action_type, partition, source, destination, destination_partition, source_disk,
                          destination_disk)
         out = C.c_int32()
-        self.lib.check(self.lib.lib.ccmi_action_acceptance_by_kind(self.handle, GOAL_KINDS[goal_name], C.byref(a),
+        self.lib.check(self.lib.lib.ccmi_action_acceptance_by_kind(self.handle, goal_kind(goal_name), C.byref(a),
                                                                    C.byref(out)))
         return ACCEPTANCE[out.value]
 
@@ -1564,7 +1598,7 @@ class ClusterModel:
     def _goals_call(self, fn, names, *args) -> None:
         """lib.check of fn(session, kinds of the goals `names`, their count, *args, first_invalid); what it raises
         carries the index the call reported as `first_invalid`."""
-        kinds = (C.c_int32 * max(1, len(names)))(*map(GOAL_KINDS.__getitem__, names))
+        kinds = (C.c_int32 * max(1, len(names)))(*map(goal_kind, names))
         bad = C.c_int64(-1)
         try:
             self.lib.check(fn(self.handle, kinds, len(names), *args, C.byref(bad)))
@@ -1891,6 +1925,41 @@ class ClusterModel:
         done = C.c_int64()
         self.lib.check(self.lib.lib.ccmi_session_apply(self.handle, arr, len(acts), C.byref(done)))
         return done.value
+
+    def _disks_of(self, broker_logdirs) -> List[int]:
+        """Desc disk indices of {broker id: logdirs}; an unknown broker id or logdir is the reference's "Invalid log
+        dirs provided for broker %d." (RemoveDisksRunnable.java:139-142)."""
+        ids = self.broker_ids()
+        index = {(ids[self.desc.disk_broker[d]], self.desc.disk_logdir[d].decode()): d
+                 for d in range(self.desc.num_disks)}
+        disks = []
+        for broker_id, logdirs in broker_logdirs.items():
+            for logdir in ([logdirs] if isinstance(logdirs, str) else logdirs):
+                if (broker_id, logdir) not in index:
+                    raise IllegalArgumentException(f"Invalid log dirs provided for broker {broker_id}.")
+                disks.append(index[(broker_id, logdir)])
+        return disks
+
+    def mark_disks_for_removal(self, broker_logdirs, capacity_threshold: float) -> None:
+        """RemoveDisksRunnable.checkCanRemoveDisks (:131-161) with capacityThreshold(DISK) = capacity_threshold, then
+        Disk.markDiskForRemoval on every named logdir (ccmi_session_mark_disks_for_removal; all or nothing).
+        broker_logdirs: {broker id: logdirs}. IllegalArgumentException with the reference's message when a check
+        fails, IllegalStateException on a session that has optimized a goal or applied actions."""
+        if not self.lib.has_remove_disks:
+            self._not_exported("ccmi_session_mark_disks_for_removal", "remove-disks needs a newer library")
+        disks = self._disks_of(broker_logdirs)
+        arr = (C.c_int32 * max(1, len(disks)))(*disks)
+        bad = C.c_int32(-1)
+        self.lib.check(self.lib.lib.ccmi_session_mark_disks_for_removal(self.handle, arr, len(disks),
+                                                                        float(capacity_threshold), C.byref(bad)))
+
+    def remove_disks(self, broker_logdirs, constraint: Optional[BalancingConstraint] = None,
+                     options: Optional[OptimizationOptions] = None) -> "OptimizerResult":
+        """RemoveDisksRunnable.workWithClusterModel (:77-129): checkCanRemoveDisks, markDiskForRemoval, then one
+        optimization with the single goal new IntraBrokerDiskCapacityGoal(true)."""
+        bc = constraint or BalancingConstraint()
+        self.mark_disks_for_removal(broker_logdirs, bc.capacity_threshold[DISK])
+        return GoalOptimizer(bc).optimizations(self, goals_from_names([REMOVE_DISKS_GOAL], bc), options)
 
     def cluster_stats(self, constraint: Optional[BalancingConstraint] = None,
                       options: Optional[OptimizationOptions] = None) -> Dict[str, object]:

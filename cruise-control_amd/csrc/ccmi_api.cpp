@@ -191,6 +191,24 @@ void validateChain(const ccmi_session* s, const int32_t* kinds, int n, const std
     throw std::invalid_argument("intra-broker goals cannot be optimized together with inter-broker goals");
 }
 
+// The disk tables of a JBOD session (Device::uploadDisks) from the host model, then the disks' utilization: at session
+// creation, and again when ccmi_session_mark_disks_for_removal changed disk capacities.
+void uploadDiskTables(ccmi_session* s) {
+  ccmi::Model& m = s->model;
+  std::vector<uint8_t> bAlive(m.B), dAlive(m.dAlive);
+  std::vector<double> rDu(m.R);
+  std::vector<float> rScore(m.R);
+  for (int b = 0; b < m.B; ++b) bAlive[b] = m.alive(b) ? 1 : 0;
+  for (int r = 0; r < m.R; ++r) {
+    rDu[r] = m.ru(r, ccmi::R_DISK);
+    rScore[r] = m.rScoreC[4 * (size_t)r + ccmi::R_DISK];
+  }
+  s->device->uploadDisks(m.D, m.bDiskOff.data(), m.bDisks.data(), m.dCap.data(), dAlive.data(), bAlive.data(),
+                         m.rOrigDisk.data(), rDu.data(), rScore.data(), m.rStatic.data());
+  s->device->setDiskUtil(m.dUtil.data());
+  m.diskDirty = false;
+}
+
 // AnalyzerUtils.getDiff (AnalyzerUtils.java:63-93) against the session's initial placement
 void buildProposals(ccmi_session* s) {
   const ccmi::Model& m = s->model;
@@ -325,20 +343,7 @@ ccmi_status ccmi_session_create(int32_t device_ordinal, const ccmi_cluster_desc*
                              m.topicCountDense.data());
     s->device->uploadLoads(m.W, m.rLoad.data(), m.bLoad.data(), m.bLnw.data(), m.bPot.data(), m.pSlots.data(),
                            m.pLeader.data());
-    if (m.D > 0) {
-      std::vector<uint8_t> bAlive(m.B), dAlive(m.dAlive);
-      std::vector<double> rDu(m.R);
-      std::vector<float> rScore(m.R);
-      for (int b = 0; b < m.B; ++b) bAlive[b] = m.alive(b) ? 1 : 0;
-      for (int r = 0; r < m.R; ++r) {
-        rDu[r] = m.ru(r, ccmi::R_DISK);
-        rScore[r] = m.rScoreC[4 * (size_t)r + ccmi::R_DISK];
-      }
-      s->device->uploadDisks(m.D, m.bDiskOff.data(), m.bDisks.data(), m.dCap.data(), dAlive.data(), bAlive.data(),
-                             m.rOrigDisk.data(), rDu.data(), rScore.data(), m.rStatic.data());
-      s->device->setDiskUtil(m.dUtil.data());
-      m.diskDirty = false;
-    }
+    if (m.D > 0) uploadDiskTables(s.get());
     if (m.sharedHosts) {  // Host._load for the chain kernels' moves, with each host's brokers (CSR)
       std::vector<int32_t> hOff(1, 0), hBrk;
       for (int h = 0; h < m.H; ++h) {
@@ -690,6 +695,63 @@ ccmi_status ccmi_session_apply(ccmi_session* s, const ccmi_action* actions, int6
     return fail(st == CCMI_OK ? CCMI_E_INVALID : st, st == CCMI_OK ? msg : g_err + "; " + msg);
   }
   return st;
+}
+
+// RemoveDisksRunnable.checkCanRemoveDisks (:131-161), then Disk.markDiskForRemoval (model/Disk.java:113-118)
+ccmi_status ccmi_session_mark_disks_for_removal(ccmi_session* s, const int32_t* disks, int32_t n,
+                                                double disk_capacity_threshold, int32_t* first_invalid) {
+  if (first_invalid) *first_invalid = -1;
+  return guarded([&] {
+    if (!s) throw std::invalid_argument("null session");
+    if (n < 0) throw std::invalid_argument("negative count");
+    if (n > 0 && !disks) throw std::invalid_argument("null argument");
+    ccmi::Model& m = s->model;
+    if (m.D == 0) throw std::invalid_argument("the model has no disks (JBOD) to remove");
+    if (!s->engine->optimized.empty() || !m.log.empty())
+      throw ccmi::StateError("disks are marked for removal on a fresh model: the session has optimized a goal or "
+                             "applied actions");
+    std::vector<uint8_t> listed((size_t)m.D, 0);
+    for (int32_t i = 0; i < n; ++i) {
+      if (disks[i] < 0 || disks[i] >= m.D) {
+        if (first_invalid) *first_invalid = i;
+        throw std::invalid_argument("disk index out of range (Invalid log dirs provided)");
+      }
+      listed[(size_t)disks[i]] = 1;
+    }
+    for (int b = 0; b < m.B; ++b) {  // the brokers named, ascending
+      int nListed = 0;
+      double futureUsage = 0.0, remainingCapacity = 0.0;
+      for (int k = m.bDiskOff[b]; k < m.bDiskOff[b + 1]; ++k) {  // broker.disks(): logdir order
+        const int d = m.bDisks[k];
+        futureUsage += m.dUtil[d];
+        if (listed[(size_t)d]) nListed++;
+        else remainingCapacity += m.dCap[d];
+      }
+      if (nListed == 0) continue;
+      char buf[128];
+      if (nListed == m.bDiskOff[b + 1] - m.bDiskOff[b]) {
+        std::snprintf(buf, sizeof(buf), "No log dir remaining to move replicas to for broker %d.", m.bId[b]);
+        throw std::invalid_argument(buf);
+      }
+      if (futureUsage / remainingCapacity > disk_capacity_threshold) {
+        std::snprintf(buf, sizeof(buf), "Not enough remaining capacity to move replicas to for broker %d.", m.bId[b]);
+        throw std::invalid_argument(buf);
+      }
+    }
+    if (n == 0) return CCMI_OK;
+    const ccmi::ThreadPin pin(s->deviceOrdinal);
+    std::vector<double> cap(m.dCap);
+    for (int d = 0; d < m.D; ++d)
+      if (listed[(size_t)d]) cap[(size_t)d] = 0.0;  // a dead disk stays dead, with capacity 0 as in the reference
+    m.dCap.swap(cap);
+    try {
+      uploadDiskTables(s);  // the one capacity table K6, stats_disks and broker_stats_disks read
+    } catch (...) {
+      m.dCap.swap(cap);  // a device failure leaves the host model as it was
+      throw;
+    }
+    return CCMI_OK;
+  });
 }
 
 ccmi_status ccmi_compute_cluster_stats(ccmi_session* s, const ccmi_balancing_constraint* c, const ccmi_opt_options* o,

@@ -351,7 +351,9 @@ class Device {
                      int32_t* intraEntries, int64_t intraCap, int32_t* leaderTasks, int64_t leaderCap);
 
   // Disks (JBOD): the static disk / replica tables once per session; setDiskUtil whenever the host changed a disk's
-  // utilization; intraRun = one intra-broker goal (K6); statsDisks = the disk part of ClusterModelStats.
+  // utilization; intraRun = one intra-broker goal (K6); statsDisks = the disk part of ClusterModelStats. uploadDisks
+  // may be called again on a session (ccmi_session_mark_disks_for_removal re-sends the tables with the new capacities;
+  // K6, stats_disks and broker_stats_disks read that one capacity table); setDiskUtil must follow it.
   void uploadDisks(int D, const int32_t* bDiskOff, const int32_t* bDisks, const double* dCap, const uint8_t* dAlive,
                    const uint8_t* bAlive, const int32_t* rOrigDisk, const double* rDu, const float* rScore,
                    const int32_t* rTie);

@@ -3,6 +3,8 @@
 // Engine::optimizeGoal); the broker loop is one K6 launch (intra.h, kernels/intra.hip) whose per-broker action records
 // the host replays, in broker-id order, into its model (ClusterModel.relocateReplica(tp, broker, logdir)).
 //   IntraBrokerDiskCapacityGoal.initGoalState / updateGoalState   IntraBrokerDiskCapacityGoal.java:81-108,223-245
+//   IntraBrokerDiskCapacityGoal(true), the goal of RemoveDisksRunnable (kind 24): the same class and name with
+//   _shouldEmptyZeroCapacityDisks set (selfSatisfied :161-173, updateGoalState :243-246, isUtilizationOverLimit :270-275)
 //   IntraBrokerDiskUsageDistributionGoal.updateGoalState           IntraBrokerDiskUsageDistributionGoal.java:106-137
 //   actionAcceptance (ccmi_action_acceptance)                      IntraBrokerDiskCapacityGoal.java:115-136,
 //                                                                  IntraBrokerDiskUsageDistributionGoal.java:146-243
@@ -34,10 +36,12 @@ class IntraGoalImpl : public GoalImpl {
  public:
   explicit IntraGoalImpl(int k) {
     kind = k;
-    ig = k == CCMI_GOAL_INTRA_BROKER_DISK_CAPACITY ? IG_CAPACITY : IG_USAGE;
+    emptyZeroCap = k == CCMI_GOAL_INTRA_BROKER_DISK_CAPACITY_EMPTY_DISKS;
+    ig = k == CCMI_GOAL_INTRA_BROKER_DISK_CAPACITY || emptyZeroCap ? IG_CAPACITY : IG_USAGE;
     name = ig == IG_CAPACITY ? "IntraBrokerDiskCapacityGoal" : "IntraBrokerDiskUsageDistributionGoal";
   }
   int ig;
+  bool emptyZeroCap;  // _shouldEmptyZeroCapacityDisks
   std::vector<double> upper, lower;  // _balanceUpperThresholdByBroker / _balanceLowerThresholdByBroker
 
   void init(Engine& e) override {
@@ -80,7 +84,10 @@ class IntraGoalImpl : public GoalImpl {
         if (!m.alive(b)) continue;
         for (int k = m.bDiskOff[b]; k < m.bDiskOff[b + 1]; ++k) {
           const int d = m.bDisks[k];
-          if (m.dAlive[d] && m.dUtil[d] > m.dCap[d] * thr) {
+          // isUtilizationOverLimit
+          const bool over = emptyZeroCap && m.dCap[d] == 0 ? m.dUtil[d] > 0 || !m.dMembers[d].empty()
+                                                           : m.dUtil[d] > m.dCap[d] * thr;
+          if (m.dAlive[d] && over) {
             ccmi_provision_recommendation rec = provisionRec();  // IntraBrokerDiskCapacityGoal.java:236-239
             rec.num_disks = 1;
             rec.total_capacity = m.dUtil[d] / thr;
@@ -90,6 +97,9 @@ class IntraGoalImpl : public GoalImpl {
                                            (int)m.dMembers[d].size(), m.bId[b]),
                                       rec);
           }
+          if (emptyZeroCap && m.dCap[d] == 0 && !m.dMembers[d].empty())  // not behind isAlive; no recommendation
+            throw OptimizationFailure(fmt2("[%s] Could not move all replicas from disk %s on broker %d", name.c_str(),
+                                           m.dLogdir[d].c_str(), m.bId[b]));
         }
       }
     } else {
@@ -171,7 +181,7 @@ bool IntraGoalImpl::rebalanceAll(Engine& e) {
   PhaseScope ps(PH_DEV_SCAN);
   Model& m = e.m;
   IntraRequest q;
-  q.goal = ig;
+  q.goal = emptyZeroCap ? IG_CAPACITY_EMPTY : ig;
   q.capThr = e.bc.capThreshold[R_DISK];
   q.margin = (e.bc.resBalance[R_DISK] - 1) * 0.9;  // BALANCE_MARGIN
   q.slot = dg.allowedSlot;
@@ -237,7 +247,8 @@ bool IntraGoalImpl::rebalanceAll(Engine& e) {
 }  // namespace
 
 bool isIntraGoalKind(int kind) {
-  return kind == CCMI_GOAL_INTRA_BROKER_DISK_CAPACITY || kind == CCMI_GOAL_INTRA_BROKER_DISK_USAGE_DISTRIBUTION;
+  return kind == CCMI_GOAL_INTRA_BROKER_DISK_CAPACITY || kind == CCMI_GOAL_INTRA_BROKER_DISK_USAGE_DISTRIBUTION ||
+         kind == CCMI_GOAL_INTRA_BROKER_DISK_CAPACITY_EMPTY_DISKS;
 }
 
 std::unique_ptr<GoalImpl> makeIntraGoal(int kind) { return std::make_unique<IntraGoalImpl>(kind); }

@@ -6,6 +6,8 @@
 //
 // Reference restated (paths under cruise-control/src/main/java/com/linkedin/kafka/cruisecontrol/):
 //   IntraBrokerDiskCapacityGoal.rebalanceForBroker          analyzer/goals/IntraBrokerDiskCapacityGoal.java:187-221
+//   IntraBrokerDiskCapacityGoal(true) (_shouldEmptyZeroCapacityDisks: selfSatisfied :161-173, isUtilizationOverLimit
+//   :270-275), the goal of RemoveDisksRunnable: IG_CAPACITY_EMPTY
 //   IntraBrokerDiskUsageDistributionGoal (init :78-104, acceptance :175-243, rebalance :254-481)
 //   AbstractGoal.maybeMoveReplicaBetweenDisks / maybeSwapReplicaBetweenDisks   analyzer/goals/AbstractGoal.java:351-430
 //   GoalUtils.legitMoveBetweenDisks :237-244, diskUtilizationPercentage :397-400, averageDiskUtilizationPercentage
@@ -26,7 +28,10 @@ namespace ccmi {
 constexpr int kIntraMaxDisks = 31;  // TimSort's binary-insertion path (MIN_MERGE = 32) covers every broker
 constexpr int kIntraHist = 16;      // queue states remembered per swap phase (cycle detection)
 constexpr int kIntraMaxPrior = 4;   // optimized intra-broker goals a session can hold
-enum IntraGoal : int32_t { IG_CAPACITY = 0, IG_USAGE = 1 };
+// IG_CAPACITY_EMPTY: IntraBrokerDiskCapacityGoal with _shouldEmptyZeroCapacityDisks. The flag rides in the goal value,
+// which every Device implementation already hands from IntraRequest.goal to IntraArgs.goal; as an optimized prior the
+// goal is IG_CAPACITY (the flag does not touch actionAcceptance).
+enum IntraGoal : int32_t { IG_CAPACITY = 0, IG_USAGE = 1, IG_CAPACITY_EMPTY = 2 };
 enum IntraStatus : int32_t { IS_OK = 0, IS_LOG_FULL = 1, IS_CYCLE = 2 };
 
 struct IntraPrior {  // an optimized intra-broker goal whose actionAcceptance every action must pass
@@ -152,7 +157,7 @@ class IntraBroker {
     for (int k = d0; k < d1; ++k) A.dUtil[A.bDisks[k]] = A.dUtilIn[A.bDisks[k]];
     for (int i = e0; i < e1; ++i) A.eDisk[i] = A.eDiskIn[i];
     nSel = A.nSel[b];
-    if (A.goal == IG_CAPACITY) capacityRebalance();
+    if (A.goal != IG_USAGE) capacityRebalance();
     else usageRebalance();
     A.logCount[b] = nLog;
     A.status[b] = status;
@@ -224,6 +229,26 @@ class IntraBroker {
   }
 #endif
 
+  // Disk._replicas.size() of disk d on the current state: every entry of the broker on the disk, selected or not. On
+  // the device the lanes split the entries 64 per step and a ballot counts them, so every lane holds the same count.
+#if defined(__HIP_DEVICE_COMPILE__)
+  __device__ int members(int d) const {
+    const int lane = threadIdx.x & 63;
+    int n = 0;
+    for (int i0 = e0; i0 < e1; i0 += 64) {
+      const int i = i0 + lane;
+      n += __popcll(__ballot(i < e1 && A.eDisk[i] == d));
+    }
+    return n;
+  }
+#else
+  int members(int d) const {
+    int n = 0;
+    for (int i = e0; i < e1; ++i) n += A.eDisk[i] == d ? 1 : 0;
+    return n;
+  }
+#endif
+
   CCMI_LD void record(int r, int src, int dst) {
     if (nLog >= logCap) {
       status = IS_LOG_FULL;
@@ -285,8 +310,9 @@ class IntraBroker {
   CCMI_LD bool moveOk(int i, int t) const {
     if (!A.dAlive[t]) return false;  // legitMoveBetweenDisks (same broker by construction)
     bool self;
-    if (A.goal == IG_CAPACITY) {
-      self = du(i) > 0 && underCap(t, du(i));
+    if (A.goal != IG_USAGE) {
+      // selfSatisfied: with the flag empty replicas move too (>= 0; NaN stays false)
+      self = (A.goal == IG_CAPACITY_EMPTY ? du(i) >= 0 : du(i) > 0) && underCap(t, du(i));
     } else {
       const double delta = -du(i);
       self = delta != 0 && usageAccept(up, lo, A.eDisk[i], t, delta);
@@ -372,23 +398,32 @@ class IntraBroker {
   }
 
   // ---------------------------------------------------------------- IntraBrokerDiskCapacityGoal
-  CCMI_LD bool over(int d) const { return A.dUtil[d] > A.dCap[d] * A.capThr; }
+  // isUtilizationOverLimit: with the flag a zero-capacity disk is over while it has utilization or any replica
+  // (mem = Disk._replicas.size() of d; read only for such a disk)
+  CCMI_LD bool emptied(int d) const { return A.goal == IG_CAPACITY_EMPTY && A.dCap[d] == 0; }
+  CCMI_LD bool over(int d, int mem) const {
+    if (emptied(d)) return A.dUtil[d] > 0 || mem > 0;
+    return A.dUtil[d] > A.dCap[d] * A.capThr;
+  }
   CCMI_LD void capacityRebalance() {
     int32_t overD[kIntraMaxDisks], cands[kIntraMaxDisks];
     int nOver = 0, nC = 0;
     for (int k = d0; k < d1; ++k) {
       const int d = A.bDisks[k];
-      if (A.dAlive[d] && over(d)) overD[nOver++] = d;
+      if (A.dAlive[d] && over(d, emptied(d) ? members(d) : 0)) overD[nOver++] = d;
       else cands[nC++] = d;
     }
     if (nOver == 0) return;
     timSortSmall(cands, nC);
     for (int k = 0; k < nOver; ++k) {
       const int d = overD[k];
+      // the replica set of an over-limit disk only shrinks, by this loop's own moves (over-limit disks are no
+      // candidates): counted once here, kept in a register
+      int mem = emptied(d) ? members(d) : 0;
       const int n = snapshot(d, true, sa);
       for (int q = 0; q < n; ++q) {
-        maybeMove(sa[q], cands, nC);
-        if (!over(d)) break;
+        if (maybeMove(sa[q], cands, nC) >= 0) --mem;
+        if (!over(d, mem)) break;
       }
     }
   }

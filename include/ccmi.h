@@ -131,7 +131,19 @@ typedef enum ccmi_goal_kind {
   CCMI_GOAL_TOPIC_LEADER_REPLICA_DISTRIBUTION = 21, /* TopicLeaderReplicaDistributionGoal (ABI v7; in goals, not in
                                                        default.goals: AnalyzerConfig.java:297-319) */
   CCMI_GOAL_KAFKA_ASSIGNER_EVEN_RACK_AWARE = 22,     /* KafkaAssignerEvenRackAwareGoal (ABI v7; in goals) */
-  CCMI_GOAL_KAFKA_ASSIGNER_DISK_USAGE_DISTRIBUTION = 23 /* KafkaAssignerDiskUsageDistributionGoal (ABI v7; in goals) */
+  CCMI_GOAL_KAFKA_ASSIGNER_DISK_USAGE_DISTRIBUTION = 23, /* KafkaAssignerDiskUsageDistributionGoal (ABI v7; in goals) */
+  CCMI_GOAL_INTRA_BROKER_DISK_CAPACITY_EMPTY_DISKS = 24  /* new IntraBrokerDiskCapacityGoal(true), the goal of
+                                                            RemoveDisksRunnable (additive at ABI v13; present exactly
+                                                            when ccmi_session_mark_disks_for_removal is). Goal.name() is
+                                                            IntraBrokerDiskCapacityGoal; an intra-broker kind wherever 16
+                                                            is one, with 16's actionAcceptance. It also empties
+                                                            zero-capacity disks: replicas of load 0 move too, such a
+                                                            disk is over its limit while it has utilization or any
+                                                            replica (an alive one that stays so fails the goal with
+                                                            the over-limit message and its numDisks(1)
+                                                            recommendation), and a dead one that keeps a replica
+                                                            fails it with "Could not move all replicas from disk
+                                                            ..." (no provision recommendation) */
 } ccmi_goal_kind;
 
 /* AnalyzerConfig replica.to.broker.set.mapping.policy.class (config/ReplicaToBrokerSetMappingPolicy.java) */
@@ -550,6 +562,22 @@ ccmi_status ccmi_swaps_acceptance_grid(ccmi_session* s, const int32_t* goal_kind
  * fails the call with CCMI_E_INVALID and `*applied` (optional) = actions applied before it. Applied actions join
  * the action log and the proposals (the diff against the session's initial placement). */
 ccmi_status ccmi_session_apply(ccmi_session* s, const ccmi_action* actions, int64_t n, int64_t* applied);
+/* RemoveDisksRunnable.checkCanRemoveDisks (:131-161), then Disk.markDiskForRemoval (capacity := 0) on every listed
+ * disk, all or nothing (additive at ABI v13; its presence is the capability flag, also of goal kind 24). `disks` are
+ * desc disk indices; duplicates are harmless. The brokers named are checked in ascending broker index, each in this
+ * order: every disk of the broker listed (dead disks count) -> CCMI_E_INVALID "No log dir remaining to move replicas to
+ * for broker %d."; futureUsage / remainingCapacity > disk_capacity_threshold -> CCMI_E_INVALID "Not enough remaining
+ * capacity to move replicas to for broker %d.", futureUsage the sum of Disk._utilization over all of the broker's disks
+ * and remainingCapacity the sum of capacity() over those not listed, both in logdir order as doubles (a dead disk's -1
+ * is added like any capacity; 0/0 and x/0 compare as in Java). A disk index out of range is CCMI_E_INVALID with
+ * *first_invalid (optional) = its position in `disks`, the reference's "Invalid log dirs provided for broker %d.";
+ * *first_invalid is -1 otherwise. CCMI_E_STATE when the session has optimized a goal or its action log is not empty
+ * (the runnable starts from a fresh model); CCMI_E_INVALID for a NULL session, n < 0, NULL disks with n > 0, or a desc
+ * without disks. On success the listed disks' capacity is 0.0 in the host model and in the device disk table (the
+ * session's disk tables are sent again); a dead disk stays dead; broker capacities do not change. Every query then answers as a
+ * fresh session created from the same desc with those disk_capacity entries 0.0. Nothing changes on failure. */
+ccmi_status ccmi_session_mark_disks_for_removal(ccmi_session* s, const int32_t* disks, int32_t n,
+                                                double disk_capacity_threshold, int32_t* first_invalid /* optional */);
 /* Goal.provisionResponse of the goal whose OptimizationFailureException (CCMI_E_OPT_FAILURE) ended the session's last
  * optimization call: UNDER_PROVISIONED with the exception's ProvisionRecommendation (AbstractGoal.java:125-130). */
 ccmi_status ccmi_last_failure_provision(const ccmi_session* s, ccmi_provision_response* out);
