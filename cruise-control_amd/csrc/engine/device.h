@@ -531,7 +531,7 @@ class Device {
   unsigned long long* dSrState_ = nullptr;
   uint8_t *dSrTopicExcl_ = nullptr, *dSrTopicIncl_ = nullptr;
   uint64_t* dSrKeys_ = nullptr;
-  SrEntry* dSrBuf_[2] = {nullptr, nullptr};
+  SortEntry* dSrBuf_[2] = {nullptr, nullptr};
   ccmi_swap_replica* dSrRecords_ = nullptr;
   double* dSrScores_ = nullptr;
   size_t srOutCap_ = 0;
@@ -546,7 +546,7 @@ class Device {
   uint32_t *dEpTiles_ = nullptr, *dEpCounts_ = nullptr, *dEpCursors_ = nullptr;
   EpSums* dEpSums_ = nullptr;
   unsigned long long* dEpState_ = nullptr;
-  EpEntry* dEpBuf_[2] = {nullptr, nullptr};
+  SortEntry* dEpBuf_[2] = {nullptr, nullptr};
   ccmi_plan_task* dEpTasks_ = nullptr;
   int32_t *dEpInterOut_ = nullptr, *dEpIntraOut_ = nullptr, *dEpLeaderOut_ = nullptr;
   size_t epBufCap_ = 0, epTaskCap_ = 0, epInterCap_ = 0, epIntraCap_ = 0, epLeaderCap_ = 0;

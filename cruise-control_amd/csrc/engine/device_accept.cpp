@@ -45,7 +45,7 @@ hipError_t launchSortedReplicasCount(const SrTables& T, const SrQuery& q, int n,
                                      hipStream_t stream);
 hipError_t launchSortedReplicasFill(const SrTables& T, const SrQuery& q, int n, const uint64_t* keys,
                                     const int32_t* segOf, uint32_t* cursor, const unsigned long long* state,
-                                    long long total, long long maxLen, SrEntry* bufA, SrEntry* bufB,
+                                    long long total, long long maxLen, SortEntry* bufA, SortEntry* bufB,
                                     ccmi_swap_replica* records, double* scores, int* launches, hipStream_t stream);
 hipError_t launchExecutionPlanCount(const EpTables& T, int tiles, EpRow* rows, uint32_t* tileInter,
                                     uint32_t* tileLeader, uint32_t* counts, uint32_t* cursors, EpSums* sums,
@@ -54,9 +54,9 @@ hipError_t launchExecutionPlanFill(const EpTables& T, const EpQuery& q, int tile
                                    const uint32_t* tileInter, const uint32_t* tileLeader, uint32_t* cursors,
                                    const unsigned long long* state, long long numInter, long long numLeader,
                                    long long interTotal, long long interMax, long long intraTotal, long long intraMax,
-                                   EpEntry* bufA, EpEntry* bufB, int32_t* idOf, ccmi_plan_task* tasks, int32_t* interOut,
-                                   int32_t* order, int32_t* intraOut, int32_t* leaderOut, int* launches,
-                                   hipStream_t stream);
+                                   SortEntry* bufA, SortEntry* bufB, int32_t* idOf, ccmi_plan_task* tasks,
+                                   int32_t* interOut, int32_t* order, int32_t* intraOut, int32_t* leaderOut,
+                                   int* launches, hipStream_t stream);
 
 namespace {
 constexpr double kAcceptWaitSeconds = 120.0;
@@ -559,8 +559,8 @@ void Device::sortedReplicas(const SrQuery& q, const int32_t* seg, int n, const u
                      (int64_t)n * 24;
   if (total > 0 && total <= capacity) {
     if (!records) throw std::logic_error("sortedReplicas: no room for the records");
-    if (maxLen > kSrSortTile && !dSrBuf_[1]) {  // a segment longer than a tile: the merge passes' second buffer
-      hipCheck(hipMalloc((void**)&dSrBuf_[1], (size_t)R_ * sizeof(SrEntry)), "hipMalloc merge buffer");
+    if (maxLen > kSegSortTile && !dSrBuf_[1]) {  // a segment longer than a tile: the merge passes' second buffer
+      hipCheck(hipMalloc((void**)&dSrBuf_[1], (size_t)R_ * sizeof(SortEntry)), "hipMalloc merge buffer");
       srAllocs_.push_back(dSrBuf_[1]);
     }
     if ((size_t)total > srOutCap_) {
@@ -591,7 +591,7 @@ void Device::sortedReplicas(const SrQuery& q, const int32_t* seg, int n, const u
     launches += fill;
     // per replica a key and a segment in; per entry one write, the sort's read and write, a read and a write per merge
     // pass, the gather's entry and replica words in and a record (and a score) out
-    perf.statsBytes += (int64_t)R_ * 12 + total * (int64_t)(sizeof(SrEntry) * (4 + 2 * (fill - 3)) + 16 + 8 + (scores ? 8 : 0));
+    perf.statsBytes += (int64_t)R_ * 12 + total * (int64_t)(sizeof(SortEntry) * (4 + 2 * (fill - 3)) + 16 + 8 + (scores ? 8 : 0));
   }
   perf.statsLaunches += launches;
 }
@@ -749,7 +749,7 @@ void Device::executionPlan(const EpQuery& q, const int32_t* curDisks, const int3
     // sorts' and merge passes' reads and writes, the gather's read and a word out
     perf.statsBytes += (int64_t)P_ * 2 * (int64_t)sizeof(EpRow) +
                        (numTasks + intraTotal) * (int64_t)(sizeof(PartitionRec) + 64) +
-                       entries * (int64_t)(sizeof(EpEntry) * (4 + 2 * std::max(0, fill - 8)) + 4) +
+                       entries * (int64_t)(sizeof(SortEntry) * (4 + 2 * std::max(0, fill - 8)) + 4) +
                        numTasks * (int64_t)sizeof(ccmi_plan_task);
   }
   if (interTotal == 0 && fits && brokerOrder)  // no broker has tasks: the whole order is "none"

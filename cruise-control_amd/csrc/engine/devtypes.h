@@ -310,17 +310,24 @@ struct PdTables {
   int32_t R, P;
 };
 
-// ccmi_sorted_replicas (kernels/sorted_replicas.hip): a broker's SortedReplicas list per asked broker. SrEntry: one
-// selected replica in the sort; the key is Model::replicaKey generalised to the priority order (bits 63 / 62: priority
-// function 0 / 1 says "not first", 61..30: the Double.compare-ordered float score bits, 29: online, 28..0: rStatic) and
-// unique among replicas. SrQuery: the Spec of a call. SrState: the device words the host reads back with the offsets.
-constexpr int kSrSortTile = 4096;  // entries one workgroup sorts in LDS (64 KB: two workgroups per CU)
-struct alignas(16) SrEntry {
-  uint64_t key;
-  int32_t r;
-  int32_t pad;
+// The segmented sort K15 and K16 share (kernels/segments.h). SortEntry: one sort entry, moved with one 16-byte access;
+// each feature orders it with its own comparator. In every order the all-ones entry is the padding and sorts last, and
+// no two entries of a segment compare equal.
+constexpr int kSegSortTile = 4096;  // entries one workgroup sorts in LDS (64 KB: two workgroups per CU)
+// The tile under the names of the two features: their tests read the figure from these two lines.
+constexpr int kSrSortTile = 4096;
+constexpr int kEpSortTile = 4096;
+static_assert(kSrSortTile == kSegSortTile && kEpSortTile == kSegSortTile, "one sort, one tile");
+struct alignas(16) SortEntry {
+  uint64_t lo, hi;
 };
-static_assert(sizeof(SrEntry) == 16, "SrEntry is one 16-byte load");
+static_assert(sizeof(SortEntry) == 16, "SortEntry is one 16-byte access");
+
+// ccmi_sorted_replicas (kernels/sorted_replicas.hip): a broker's SortedReplicas list per asked broker. A selected replica
+// is the SortEntry {lo = key, hi = replica id}, ordered by the key and then the id's 32 bits; the key is
+// Model::replicaKey generalised to the priority order (bits 63 / 62: priority function 0 / 1 says "not first", 61..30:
+// the Double.compare-ordered float score bits, 29: online, 28..0: rStatic) and unique among replicas. SrQuery: the Spec
+// of a call. SrState: the device words the host reads back with the offsets.
 constexpr uint64_t kSrNotSelected = ~0ull;  // no replica's key: the score field is all ones only for a NaN
 struct SrQuery {
   int32_t selectMask;   // CCMI_SEL_* bits
@@ -348,21 +355,17 @@ struct SrTables {
 };
 
 // ccmi_execution_plan (kernels/execution_plan.hip): what ExecutionTaskPlanner.addExecutionProposals builds from the
-// proposals of K14. EpRow: one partition's tasks as the classify kernel leaves them. EpEntry: one sort entry, a 128-bit
-// key compared hi then lo; every list's payload is the key's own low bits (an execution id or a partition index), and no
-// two entries of a segment share a key. EpQuery: the chain as the kernels apply it: the strategies before BASE, a second
-// size strategy dropped (it never decides after the first). EpSums: the device sums behind ccmi_plan_summary.
-constexpr int kEpSortTile = 4096;  // entries one workgroup sorts in LDS (64 KB), as kSrSortTile
+// proposals of K14. EpRow: one partition's tasks as the classify kernel leaves them. Its sort entries are SortEntry as
+// a 128-bit key compared hi then lo; every list's payload is the key's own low bits (an execution id or a partition
+// index). EpQuery: the chain as the kernels apply it: the strategies before BASE, a second size strategy dropped (it
+// never decides after the first). EpSums: the device sums behind ccmi_plan_summary.
 enum : int32_t { EP_INTER = 1, EP_LEADER = 2 };  // EpRow.flags bits 0 / 1; bits 8..11 num_to_add, 12..15 between disks
 struct alignas(16) EpRow {
   int32_t flags;
   int32_t src;   // the old leader's broker: the broker an inter-broker task is filed under besides its destinations
   int64_t data;  // ExecutionProposal.dataToMoveInMB
 };
-struct alignas(16) EpEntry {
-  uint64_t lo, hi;
-};
-static_assert(sizeof(EpRow) == 16 && sizeof(EpEntry) == 16, "one 16-byte access each");
+static_assert(sizeof(EpRow) == 16, "one 16-byte access");
 struct EpQuery {
   int32_t n;         // strategies that can decide before the execution id
   int32_t strat[4];  // CCMI_STRATEGY_* (never BASE)

@@ -9,10 +9,10 @@
 //                               inter-broker and of leadership tasks, per broker the number of inter-broker and of
 //                               intra-broker list entries (the lanes of a wave that share a broker add once), and the
 //                               summary sums (wave -> LDS -> one set of 64-bit atomics per workgroup).
-//     execution_plan_scan     : four independent workgroups: the exclusive scans of the two tile-count arrays, and of
-//                               the two per-broker count arrays into offsets, totals and longest segments (cursors
-//                               cleared). When any intra-broker task exists the inter-broker lists are empty
-//                               (maybeDropReplicaSwapTasks): their counts read as zero.
+//     execution_plan_scan     : four independent workgroups: the exclusive scans of the two tile-count arrays, and
+//                               segmentOffsets (segments.h) on the two per-broker count arrays: offsets, totals and
+//                               longest segments, cursors cleared. When any intra-broker task exists the inter-broker
+//                               lists are empty (maybeDropReplicaSwapTasks): their counts read as zero.
 //     execution_plan_number   : the task partitions compacted in partition order (ballot ranks, as K14's gather) into
 //                               {rank, partition} keys, for the inter-broker and the leadership tasks. With a
 //                               proposal_rank the two lists are then sorted as one segment each by the sort below.
@@ -22,11 +22,9 @@
 //                               chain's fields most significant first, ending in the execution id) goes to the segments
 //                               of the old leader and of every added broker, an intra-broker task's {rank, partition}
 //                               key to the segment of its broker (wave-aggregated cursors).
-//     execution_plan_sort     : K15's segmented bitonic sort in LDS on 128-bit keys: the network is as wide as the
-//                               segment's next power of two, the 4 KB instance serves calls whose longest segment has at
-//                               most 256 entries, a longer segment is sorted tile by tile and finished by
-//     execution_plan_merge    : K15's global merge passes, ping-pong between two buffers; a segment of length len ends
-//                               in buffer passes(len) & 1.
+//     launchSegSort           : the shared segmented sort (segments.h) under EpLess, once per list: an LDS bitonic
+//                               sort per segment and, for a segment longer than kSegSortTile, merge passes into the
+//                               second buffer; a segment of length len ends in buffer (segSortPasses(len) & 1).
 //     execution_plan_order    : one lane per broker: its rank among the brokers with tasks under (first task's key, the
 //                               longer list, the smaller index) by counting the tuples below its own, staged through
 //                               LDS 256 at a time. The tuples are distinct, so the ranks are a permutation.
@@ -42,6 +40,7 @@
 #include "ccmi.h"
 #include "../engine/devtypes.h"
 #include "proposal_row.h"
+#include "segments.h"
 
 namespace ccmi {
 
@@ -52,39 +51,9 @@ constexpr int kEpWaves = kEpBlock / 64;
 constexpr int kEpRounds = kPdTile / kEpBlock;
 constexpr int kEpMaxBlocks = 1024;
 constexpr int kEpScanBlock = 1024;
-constexpr int kEpSmallTile = 256;   // the LDS image of a call whose longest segment fits it: 4 KB
-constexpr int kEpSmallBlock = 128;  // and its workgroup
 constexpr int kEpSums = 6;
 
 static_assert(sizeof(ccmi_plan_task) == 16 && sizeof(ccmi_plan_summary) == 64 && sizeof(EpSums) == 64, "record sizes");
-static_assert((kEpSortTile & (kEpSortTile - 1)) == 0 && kEpSortTile * sizeof(EpEntry) <= 64 * 1024, "tile shape");
-
-__device__ __forceinline__ unsigned long long epWaveSum(unsigned long long v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += (unsigned long long)__shfl_xor((long long)v, s, 64);
-  return v;
-}
-
-// The lanes of a wave with `active` set add one each to counters[seg]: one atomic per distinct segment in the wave.
-// Returns the lane's slot among the counter's arrivals. Every lane of the wave calls it (the loop is wave-uniform).
-__device__ __forceinline__ uint32_t epWaveSegAdd(uint32_t* __restrict__ counters, int seg, bool active) {
-  const int lane = (int)(threadIdx.x & 63);
-  const unsigned long long below = (1ull << lane) - 1ull;
-  unsigned long long todo = __ballot(active);
-  uint32_t slot = 0;
-  while (todo) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const int s = __shfl(seg, leader, 64);
-    const bool mine = active && seg == s;
-    const unsigned long long m = __ballot(mine);
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(&counters[s], (uint32_t)__popcll(m));
-    base = (uint32_t)__shfl((int)base, leader, 64);
-    if (mine) slot = base + (uint32_t)__popcll(m & below);
-    todo &= ~m;
-  }
-  return slot;
-}
 
 // slot k of the new replicas: a replica to add (its broker is no old broker), or one to move between disks (an old
 // broker, a new (broker, disk) pair): ExecutionProposal.java:74, :76-78
@@ -120,7 +89,7 @@ __device__ __forceinline__ void epPush(uint64_t& hi, uint64_t& lo, int bits, uin
 // PostponeUrpReplicaMovementStrategy.java:47-50 (not under-replicated first), PrioritizeMinIsrWithOfflineReplicasStrategy
 // .java:46-53 (under min-ISR, then at min-ISR, then the rest), PrioritizeOneAboveMinIsrWithOfflineReplicasStrategy.java:
 // 44-49 (one above min-ISR first); the size comparators on the int64 value, descending or ascending; BASE last.
-__device__ __forceinline__ EpEntry epTaskKey(const EpQuery& q, uint32_t st, int64_t data, uint32_t id) {
+__device__ __forceinline__ SortEntry epTaskKey(const EpQuery& q, uint32_t st, int64_t data, uint32_t id) {
   uint64_t hi = 0, lo = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -140,65 +109,32 @@ __device__ __forceinline__ EpEntry epTaskKey(const EpQuery& q, uint32_t st, int6
     }
   }
   epPush(hi, lo, 31, id & 0x7fffffffu);
-  EpEntry e;
+  SortEntry e;
   e.lo = lo;
   e.hi = hi;
   return e;
 }
 
-// an entry as a uint4: x, y = lo; z, w = hi
-__device__ __forceinline__ bool epLess(const uint4& a, const uint4& b) {
-  const uint64_t ah = ((uint64_t)a.w << 32) | a.z, bh = ((uint64_t)b.w << 32) | b.z;
-  if (ah != bh) return ah < bh;
-  return (((uint64_t)a.y << 32) | a.x) < (((uint64_t)b.y << 32) | b.x);
-}
-
-// the segment of entry k: the last i with offsets[i] <= k (empty segments repeat an offset and are skipped)
-__device__ __forceinline__ int epSegmentOf(const unsigned long long* __restrict__ offsets, int n, long long k) {
-  int lo = 0, hi = n;  // invariant: offsets[lo] <= k < offsets[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if ((long long)offsets[mid] <= k)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-__device__ __host__ __forceinline__ int epPasses(long long len) {
-  int p = 0;
-  for (long long w = kEpSortTile; w < len; w <<= 1) p++;
-  return p;
-}
-
-// a broker's list length and, when it has one, its first task's key (the sorted segment is in buffer passes(len) & 1)
+// a broker's list length and, when it has one, its first task's key (the sorted segment is in buffer segSortPasses(len) & 1)
 __device__ __forceinline__ uint32_t epHeadLen(const unsigned long long* __restrict__ offsets, int B, int b) {
   return b < B ? (uint32_t)(offsets[b + 1] - offsets[b]) : 0u;
 }
 __device__ __forceinline__ uint4 epHeadKey(const unsigned long long* __restrict__ offsets, int b, uint32_t len,
-                                           const EpEntry* __restrict__ bufA, const EpEntry* __restrict__ bufB) {
+                                           const SortEntry* __restrict__ bufA, const SortEntry* __restrict__ bufB) {
   if (len == 0) return make_uint4(0, 0, 0, 0);
-  return *reinterpret_cast<const uint4*>(((epPasses((long long)len) & 1) ? bufB : bufA) + offsets[b]);
-}
-
-// exclusive scan of counts[0, n) by one workgroup; a thread sums a contiguous chunk. Returns the thread's exclusive
-// prefix; *total is the sum (valid in every thread).
-__device__ __forceinline__ unsigned long long epBlockScan(unsigned long long (*s)[kEpScanBlock], unsigned long long sum,
-                                                          unsigned long long* total) {
-  int cur = 0;
-  s[0][threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < kEpScanBlock; d <<= 1) {
-    const unsigned long long v = s[cur][threadIdx.x] + ((int)threadIdx.x >= d ? s[cur][threadIdx.x - d] : 0ull);
-    s[cur ^ 1][threadIdx.x] = v;
-    cur ^= 1;
-    __syncthreads();
-  }
-  *total = s[cur][kEpScanBlock - 1];
-  return s[cur][threadIdx.x] - sum;
+  return *reinterpret_cast<const uint4*>(((segSortPasses((long long)len) & 1) ? bufB : bufA) + offsets[b]);
 }
 
 }  // namespace
+
+// the order of every list: the 128-bit key, hi then lo (an entry as a uint4: x, y = lo; z, w = hi)
+struct EpLess {
+  static __device__ __forceinline__ bool less(const uint4& a, const uint4& b) {
+    const uint64_t ah = ((uint64_t)a.w << 32) | a.z, bh = ((uint64_t)b.w << 32) | b.z;
+    if (ah != bh) return ah < bh;
+    return (((uint64_t)a.y << 32) | a.x) < (((uint64_t)b.y << 32) | b.x);
+  }
+};
 
 __global__ __launch_bounds__(kEpBlock) void execution_plan_classify(EpTables T, int tiles, EpRow* __restrict__ rows,
                                                                     uint32_t* __restrict__ tileInter,
@@ -253,7 +189,7 @@ __global__ __launch_bounds__(kEpBlock) void execution_plan_classify(EpTables T, 
       {
         const int b = inter ? w.oldLeader : -1;
         const bool ok = (unsigned)b < (unsigned)T.B;
-        (void)epWaveSegAdd(interCnt, b, ok);
+        (void)waveSegAdd(interCnt, b, ok);
         acc[1] += ok ? 1 : 0;
       }
 #pragma unroll
@@ -263,13 +199,13 @@ __global__ __launch_bounds__(kEpBlock) void execution_plan_classify(EpTables T, 
         const int b = w.newR[x];
         const bool inRange = (unsigned)b < (unsigned)T.B;
         const bool okA = w.changed && inter && added && inRange;
-        (void)epWaveSegAdd(interCnt, b, okA);
+        (void)waveSegAdd(interCnt, b, okA);
         acc[1] += okA ? 1 : 0;
-        (void)epWaveSegAdd(intraCnt, b, w.changed && between && inRange);
+        (void)waveSegAdd(intraCnt, b, w.changed && between && inRange);
       }
     }
-    cntI = (uint32_t)epWaveSum(cntI);
-    cntL = (uint32_t)epWaveSum(cntL);
+    cntI = (uint32_t)waveSum(cntI);
+    cntL = (uint32_t)waveSum(cntL);
     if (lane == 0) {
       tileCnt[0][wave] = cntI;
       tileCnt[1][wave] = cntL;
@@ -283,7 +219,7 @@ __global__ __launch_bounds__(kEpBlock) void execution_plan_classify(EpTables T, 
     __syncthreads();
   }
 #pragma unroll
-  for (int k = 0; k < kEpSums; ++k) acc[k] = epWaveSum(acc[k]);
+  for (int k = 0; k < kEpSums; ++k) acc[k] = waveSum(acc[k]);
   __syncthreads();  // sh is zeroed (a workgroup without a tile has not passed a barrier yet)
   if (lane == 0)
     for (int k = 0; k < kEpSums; ++k)
@@ -303,21 +239,10 @@ __global__ __launch_bounds__(kEpScanBlock) void execution_plan_scan(int tiles, u
                                                                     uint32_t* __restrict__ cursors,
                                                                     const EpSums* __restrict__ sums,
                                                                     unsigned long long* __restrict__ state) {
-  __shared__ unsigned long long s[2][kEpScanBlock];
-  __shared__ uint32_t mx;
   const bool dropped = sums->v[2] > 0;  // maybeDropReplicaSwapTasks
   if (blockIdx.x < 2) {
     uint32_t* counts = blockIdx.x == 0 ? tileInter : tileLeader;
-    const int chunk = (tiles + kEpScanBlock - 1) / kEpScanBlock;
-    const int i0 = min(tiles, (int)threadIdx.x * chunk), i1 = min(tiles, i0 + chunk);
-    unsigned long long sum = 0, total;
-    for (int i = i0; i < i1; ++i) sum += counts[i];
-    unsigned long long run = epBlockScan(s, sum, &total);
-    for (int i = i0; i < i1; ++i) {
-      const uint32_t c = counts[i];
-      counts[i] = (uint32_t)run;
-      run += c;
-    }
+    const unsigned long long total = scanCountsInPlace<unsigned long long, kEpScanBlock>(counts, tiles);
     if (threadIdx.x == 0) {
       counts[tiles] = (uint32_t)total;
       unsigned long long* off = state + 2 * ((size_t)B + 3) + 2 * blockIdx.x;
@@ -328,33 +253,8 @@ __global__ __launch_bounds__(kEpScanBlock) void execution_plan_scan(int tiles, u
   }
   if (blockIdx.x > 3) return;
   const int list = (int)blockIdx.x - 2;
-  const uint32_t* counts = list == 0 ? interCnt : intraCnt;
-  const bool zero = list == 0 && dropped;
-  uint32_t* cursor = cursors + (size_t)list * B;
-  unsigned long long* st = state + (size_t)list * ((size_t)B + 3);
-  if (threadIdx.x == 0) mx = 0;
-  const int chunk = (B + kEpScanBlock - 1) / kEpScanBlock;
-  const int i0 = min(B, (int)threadIdx.x * chunk), i1 = min(B, i0 + chunk);
-  unsigned long long sum = 0, total;
-  uint32_t longest = 0;
-  for (int i = i0; i < i1; ++i) {
-    const uint32_t c = zero ? 0u : counts[i];
-    sum += c;
-    longest = c > longest ? c : longest;
-    cursor[i] = 0;
-  }
-  __syncthreads();
-  if (longest) atomicMax(&mx, longest);
-  unsigned long long run = epBlockScan(s, sum, &total);  // its barriers come after every atomicMax
-  for (int i = i0; i < i1; ++i) {
-    st[2 + i] = run;
-    run += zero ? 0u : counts[i];
-  }
-  if (threadIdx.x == 0) {
-    st[0] = total;
-    st[1] = mx;
-    st[2 + B] = total;
-  }
+  segmentOffsets<kEpScanBlock>(list == 0 ? interCnt : intraCnt, B, list == 0 && dropped,
+                               state + (size_t)list * ((size_t)B + 3), cursors + (size_t)list * B);
 }
 
 // The task partitions in partition order: entry rank = the tile's offset + the tasks of the tile's earlier rounds + those
@@ -363,8 +263,8 @@ __global__ __launch_bounds__(kEpBlock) void execution_plan_number(int P, int til
                                                                   const int32_t* __restrict__ rank,
                                                                   const uint32_t* __restrict__ tileInter,
                                                                   const uint32_t* __restrict__ tileLeader, int doInter,
-                                                                  EpEntry* __restrict__ interList,
-                                                                  EpEntry* __restrict__ leaderList) {
+                                                                  SortEntry* __restrict__ interList,
+                                                                  SortEntry* __restrict__ leaderList) {
   __shared__ uint32_t waveCnt[2][kEpWaves];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const unsigned long long below = (1ull << lane) - 1ull;
@@ -393,7 +293,7 @@ __global__ __launch_bounds__(kEpBlock) void execution_plan_number(int P, int til
         totalL += waveCnt[1][x];
       }
       if (isI || isL) {
-        EpEntry e;
+        SortEntry e;
         e.hi = 0;
         e.lo = epOrderKey(rank, p);
         const uint32_t ri = runI + beforeI + (uint32_t)__popcll(mI & below);
@@ -409,9 +309,9 @@ __global__ __launch_bounds__(kEpBlock) void execution_plan_number(int P, int til
 }
 
 __global__ __launch_bounds__(kEpBlock) void execution_plan_ids(int P, const EpRow* __restrict__ rows, long long numInter,
-                                                               const EpEntry* __restrict__ interList,
+                                                               const SortEntry* __restrict__ interList,
                                                                long long numLeader,
-                                                               const EpEntry* __restrict__ leaderList,
+                                                               const SortEntry* __restrict__ leaderList,
                                                                int32_t* __restrict__ idOf,
                                                                ccmi_plan_task* __restrict__ tasks,
                                                                int32_t* __restrict__ leaderOut) {
@@ -442,8 +342,8 @@ __global__ __launch_bounds__(kEpBlock) void execution_plan_scatter(EpTables T, E
                                                                    const unsigned long long* __restrict__ interOff,
                                                                    const unsigned long long* __restrict__ intraOff,
                                                                    uint32_t* __restrict__ cursors,
-                                                                   EpEntry* __restrict__ interEntries,
-                                                                   EpEntry* __restrict__ intraEntries) {
+                                                                   SortEntry* __restrict__ interEntries,
+                                                                   SortEntry* __restrict__ intraEntries) {
   uint32_t* curInter = cursors;
   uint32_t* curIntra = cursors + T.B;
   const int stride = gridDim.x * kEpBlock;
@@ -457,7 +357,7 @@ __global__ __launch_bounds__(kEpBlock) void execution_plan_scatter(EpTables T, E
     if (p < T.pd.P) row = rows[p];
     const bool inter = doInter && (row.flags & EP_INTER);
     const bool has = inter || ((row.flags >> 12) & 15) != 0;
-    EpEntry key, okey;
+    SortEntry key, okey;
     key.lo = key.hi = okey.lo = okey.hi = 0;
     if (has) {
       pdDiff(T.pd, p, w);
@@ -467,7 +367,7 @@ __global__ __launch_bounds__(kEpBlock) void execution_plan_scatter(EpTables T, E
     {
       const int b = inter ? row.src : -1;
       const bool ok = (unsigned)b < (unsigned)T.B;
-      const uint32_t slot = epWaveSegAdd(curInter, b, ok);
+      const uint32_t slot = waveSegAdd(curInter, b, ok);
       if (ok) {
         const unsigned long long at = interOff[b] + slot;
         if (at < interOff[b + 1]) interEntries[at] = key;  // always: the counts came from the same rows
@@ -480,13 +380,13 @@ __global__ __launch_bounds__(kEpBlock) void execution_plan_scatter(EpTables T, E
       const int b = w.newR[x];
       const bool inRange = (unsigned)b < (unsigned)T.B;
       const bool okA = has && inter && added && inRange;
-      const uint32_t slotA = epWaveSegAdd(curInter, b, okA);
+      const uint32_t slotA = waveSegAdd(curInter, b, okA);
       if (okA) {
         const unsigned long long at = interOff[b] + slotA;
         if (at < interOff[b + 1]) interEntries[at] = key;
       }
       const bool okB = has && between && inRange;
-      const uint32_t slotB = epWaveSegAdd(curIntra, b, okB);
+      const uint32_t slotB = waveSegAdd(curIntra, b, okB);
       if (okB) {
         const unsigned long long at = intraOff[b] + slotB;
         if (at < intraOff[b + 1]) intraEntries[at] = okey;
@@ -495,91 +395,11 @@ __global__ __launch_bounds__(kEpBlock) void execution_plan_scatter(EpTables T, E
   }
 }
 
-// kLds: the entries of the workgroup's LDS image. The launcher picks kEpSmallTile when the longest segment of the call
-// fits it, else the whole tile; the tile stride of a longer segment is kEpSortTile either way.
-template <int kLds>
-__global__ __launch_bounds__(kEpBlock) void execution_plan_sort(const unsigned long long* __restrict__ offsets,
-                                                                EpEntry* __restrict__ entries) {
-  __shared__ uint4 tile[kLds];
-  const unsigned long long off0 = offsets[blockIdx.x];
-  const long long len = (long long)(offsets[blockIdx.x + 1] - off0);
-  if (len < 2) return;
-  for (long long t0 = 0; t0 < len; t0 += kEpSortTile) {  // one tile unless the segment is longer than a tile
-    const int m = (int)min((long long)kEpSortTile, len - t0);
-    if (m > kLds) return;  // not reachable: the launcher chose kLds from the longest segment
-    uint4* seg = reinterpret_cast<uint4*>(entries + off0 + t0);
-    int width = 2;
-    while (width < m) width <<= 1;
-    for (int i = (int)threadIdx.x; i < width; i += (int)blockDim.x)
-      tile[i] = i < m ? seg[i] : make_uint4(~0u, ~0u, ~0u, ~0u);
-    __syncthreads();
-    const int half = width >> 1;
-    for (int k = 2; k <= width; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int t = (int)threadIdx.x; t < half; t += (int)blockDim.x) {
-          const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-          const int p = i | j;
-          const uint4 a = tile[i], b = tile[p];
-          const bool up = (i & k) == 0;
-          if (epLess(b, a) == up) {
-            tile[i] = b;
-            tile[p] = a;
-          }
-        }
-        __syncthreads();
-      }
-    for (int i = (int)threadIdx.x; i < m; i += (int)blockDim.x) seg[i] = tile[i];
-    __syncthreads();
-  }
-}
-
-// pass `pass` merges runs of width kEpSortTile << pass; it reads buffer (pass & 1) and writes the other
-__global__ __launch_bounds__(kEpBlock) void execution_plan_merge(const unsigned long long* __restrict__ offsets, int n,
-                                                                 long long total, int pass, EpEntry* __restrict__ bufA,
-                                                                 EpEntry* __restrict__ bufB) {
-  const long long w = (long long)kEpSortTile << pass;
-  const uint4* src = reinterpret_cast<const uint4*>((pass & 1) ? bufB : bufA);
-  uint4* dst = reinterpret_cast<uint4*>((pass & 1) ? bufA : bufB);
-  const long long stride = (long long)gridDim.x * kEpBlock;
-  for (long long k = (long long)blockIdx.x * kEpBlock + threadIdx.x; k < total; k += stride) {
-    const int sg = epSegmentOf(offsets, n, k);
-    const long long off = (long long)offsets[sg], len = (long long)offsets[sg + 1] - off;
-    if (len <= w) continue;  // sorted already; stays in the buffer of its last pass
-    const long long j = k - off;
-    const long long L = j / (2 * w) * (2 * w);
-    const long long mid = min(L + w, len), end = min(L + 2 * w, len);
-    const uint4 e = src[k];
-    long long rank;
-    if (j < mid) {  // left run: the entries before it, plus the right run's entries below it
-      long long lo = mid, hi = end;
-      while (lo < hi) {
-        const long long c = (lo + hi) >> 1;
-        if (epLess(src[off + c], e))
-          lo = c + 1;
-        else
-          hi = c;
-      }
-      rank = (j - L) + (lo - mid);
-    } else {  // right run (keys are unique: no tie to break)
-      long long lo = L, hi = mid;
-      while (lo < hi) {
-        const long long c = (lo + hi) >> 1;
-        if (epLess(src[off + c], e))
-          lo = c + 1;
-        else
-          hi = c;
-      }
-      rank = (j - mid) + (lo - L);
-    }
-    dst[off + L + rank] = e;  // L + rank < end <= len
-  }
-}
-
 // brokerComparator's initial order (ExecutionTaskPlanner.java:518-539) over the brokers with tasks: the chain on the
 // first tasks (equal keys are the same task), then the longer list, then the smaller index. order is preset to -1.
 __global__ __launch_bounds__(kEpBlock) void execution_plan_order(const unsigned long long* __restrict__ offsets, int B,
-                                                                 const EpEntry* __restrict__ bufA,
-                                                                 const EpEntry* __restrict__ bufB,
+                                                                 const SortEntry* __restrict__ bufA,
+                                                                 const SortEntry* __restrict__ bufB,
                                                                  int32_t* __restrict__ order) {
   __shared__ uint4 headKey[kEpBlock];
   __shared__ uint32_t headLen[kEpBlock];
@@ -599,9 +419,9 @@ __global__ __launch_bounds__(kEpBlock) void execution_plan_order(const unsigned 
         if (ol == 0) continue;
         const uint4 ok = headKey[j];
         bool first;  // broker c0 + j comes before b
-        if (epLess(ok, myKey))
+        if (EpLess::less(ok, myKey))
           first = true;
-        else if (epLess(myKey, ok))
+        else if (EpLess::less(myKey, ok))
           first = false;
         else
           first = ol != myLen ? ol > myLen : c0 + j < b;
@@ -615,8 +435,8 @@ __global__ __launch_bounds__(kEpBlock) void execution_plan_order(const unsigned 
 // out[k] = the low bits of entry k (mask: an execution id's 31 bits, or a partition index's 32): four per lane
 __global__ __launch_bounds__(kEpBlock) void execution_plan_gather(const unsigned long long* __restrict__ offsets, int n,
                                                                   long long total, int anyLong, uint32_t mask,
-                                                                  const EpEntry* __restrict__ bufA,
-                                                                  const EpEntry* __restrict__ bufB,
+                                                                  const SortEntry* __restrict__ bufA,
+                                                                  const SortEntry* __restrict__ bufB,
                                                                   int32_t* __restrict__ out) {
   const long long stride = (long long)gridDim.x * kEpBlock;
   for (long long quad = (long long)blockIdx.x * kEpBlock + threadIdx.x; 4 * quad < total; quad += stride) {
@@ -626,10 +446,10 @@ __global__ __launch_bounds__(kEpBlock) void execution_plan_gather(const unsigned
     for (int h = 0; h < 4; ++h) {
       if (h < cnt) {
         const long long k = 4 * quad + h;
-        const EpEntry* buf = bufA;
+        const SortEntry* buf = bufA;
         if (anyLong) {
-          const int sg = epSegmentOf(offsets, n, k);
-          if (epPasses((long long)(offsets[sg + 1] - offsets[sg])) & 1) buf = bufB;
+          const int sg = segmentOf(offsets, n, k);
+          if (segSortPasses((long long)(offsets[sg + 1] - offsets[sg])) & 1) buf = bufB;
         }
         v[h] = (int32_t)((uint32_t)buf[k].lo & mask);
       }
@@ -643,29 +463,6 @@ __global__ __launch_bounds__(kEpBlock) void execution_plan_gather(const unsigned
     }
   }
 }
-
-namespace {
-
-// sort the n segments of `offsets` (total entries, the longest maxLen) in bufA, merge passes through bufB
-int epSortSegments(const unsigned long long* offsets, int n, long long total, long long maxLen, EpEntry* bufA,
-                   EpEntry* bufB, hipStream_t stream) {
-  if (maxLen <= kEpSmallTile)
-    hipLaunchKernelGGL(execution_plan_sort<kEpSmallTile>, dim3((unsigned)n), dim3(kEpSmallBlock), 0, stream, offsets,
-                       bufA);
-  else
-    hipLaunchKernelGGL(execution_plan_sort<kEpSortTile>, dim3((unsigned)n), dim3(kEpBlock), 0, stream, offsets, bufA);
-  int nl = 1;
-  const int eblocks = (int)std::min<long long>(kEpMaxBlocks, (total + kEpBlock - 1) / kEpBlock);
-  int pass = 0;
-  for (long long w = kEpSortTile; w < maxLen; w <<= 1, ++pass) {
-    hipLaunchKernelGGL(execution_plan_merge, dim3((unsigned)eblocks), dim3(kEpBlock), 0, stream, offsets, n, total, pass,
-                       bufA, bufB);
-    nl++;
-  }
-  return nl;
-}
-
-}  // namespace
 
 // First half of a call on stream st: sums and counts cleared, classify, scan. The host then reads sums and state back.
 // counts and cursors hold 2 * B words (inter, intra); state 2 * (B + 3) + 4 words.
@@ -698,9 +495,9 @@ hipError_t launchExecutionPlanFill(const EpTables& T, const EpQuery& q, int tile
                                    const uint32_t* tileInter, const uint32_t* tileLeader, uint32_t* cursors,
                                    const unsigned long long* state, long long numInter, long long numLeader,
                                    long long interTotal, long long interMax, long long intraTotal, long long intraMax,
-                                   EpEntry* bufA, EpEntry* bufB, int32_t* idOf, ccmi_plan_task* tasks, int32_t* interOut,
-                                   int32_t* order, int32_t* intraOut, int32_t* leaderOut, int* launches,
-                                   hipStream_t stream) {
+                                   SortEntry* bufA, SortEntry* bufB, int32_t* idOf, ccmi_plan_task* tasks,
+                                   int32_t* interOut, int32_t* order, int32_t* intraOut, int32_t* leaderOut,
+                                   int* launches, hipStream_t stream) {
   const int P = T.pd.P, B = T.B;
   if (numInter < 0 || numInter > P || numLeader < 0 || numLeader > P || interTotal < 0 || intraTotal < 0 ||
       interMax > interTotal || intraMax > intraTotal || numInter + numLeader + interTotal + intraTotal < 1 || !rows ||
@@ -712,10 +509,10 @@ hipError_t launchExecutionPlanFill(const EpTables& T, const EpQuery& q, int tile
   const unsigned long long* intraOff = state + ((size_t)B + 3) + 2;
   const unsigned long long* numOff = state + 2 * ((size_t)B + 3);
   const unsigned long long* leadOff = numOff + 2;
-  EpEntry *numA = bufA, *numB = bufB;
-  EpEntry *leadA = bufA + numInter, *leadB = bufB + numInter;
-  EpEntry *interA = leadA + numLeader, *interB = leadB + numLeader;
-  EpEntry *intraA = interA + interTotal, *intraB = interB + interTotal;
+  SortEntry *numA = bufA, *numB = bufB;
+  SortEntry *leadA = bufA + numInter, *leadB = bufB + numInter;
+  SortEntry *interA = leadA + numLeader, *interB = leadB + numLeader;
+  SortEntry *intraA = interA + interTotal, *intraB = interB + interTotal;
   int nl = 0;
   hipError_t e = hipMemsetAsync(order, 0xff, (size_t)B * sizeof(int32_t), stream);
   if (e != hipSuccess) return e;
@@ -725,15 +522,15 @@ hipError_t launchExecutionPlanFill(const EpTables& T, const EpQuery& q, int tile
     hipLaunchKernelGGL(execution_plan_number, dim3((unsigned)std::min(kEpMaxBlocks, tiles)), dim3(kEpBlock), 0, stream, P,
                        tiles, rows, T.rank, tileInter, tileLeader, doInter, numA, leadA);
     nl++;
-    const EpEntry *numSorted = numA, *leadSorted = leadA;
+    const SortEntry *numSorted = numA, *leadSorted = leadA;
     if (T.rank) {  // the caller's order; without one the compaction is in order already
       if (numInter > 1) {
-        nl += epSortSegments(numOff, 1, numInter, numInter, numA, numB, stream);
-        if (epPasses(numInter) & 1) numSorted = numB;
+        nl += launchSegSort<EpLess>(numOff, 1, numInter, numInter, numA, numB, stream);
+        if (segSortPasses(numInter) & 1) numSorted = numB;
       }
       if (numLeader > 1) {
-        nl += epSortSegments(leadOff, 1, numLeader, numLeader, leadA, leadB, stream);
-        if (epPasses(numLeader) & 1) leadSorted = leadB;
+        nl += launchSegSort<EpLess>(leadOff, 1, numLeader, numLeader, leadA, leadB, stream);
+        if (segSortPasses(numLeader) & 1) leadSorted = leadB;
       }
     }
     const int iblocks = (int)std::min<long long>(kEpMaxBlocks, (numInter + numLeader + kEpBlock - 1) / kEpBlock);
@@ -747,22 +544,22 @@ hipError_t launchExecutionPlanFill(const EpTables& T, const EpQuery& q, int tile
     nl++;
   }
   if (interTotal > 0) {
-    nl += epSortSegments(interOff, B, interTotal, interMax, interA, interB, stream);
+    nl += launchSegSort<EpLess>(interOff, B, interTotal, interMax, interA, interB, stream);
     hipLaunchKernelGGL(execution_plan_order, dim3((unsigned)((B + kEpBlock - 1) / kEpBlock)), dim3(kEpBlock), 0, stream,
                        interOff, B, interA, interB, order);
     const long long quads = (interTotal + 3) / 4;
     hipLaunchKernelGGL(execution_plan_gather,
                        dim3((unsigned)std::min<long long>(kEpMaxBlocks, (quads + kEpBlock - 1) / kEpBlock)),
-                       dim3(kEpBlock), 0, stream, interOff, B, interTotal, interMax > kEpSortTile ? 1 : 0, 0x7fffffffu,
+                       dim3(kEpBlock), 0, stream, interOff, B, interTotal, interMax > kSegSortTile ? 1 : 0, 0x7fffffffu,
                        interA, interB, interOut);
     nl += 2;
   }
   if (intraTotal > 0) {
-    nl += epSortSegments(intraOff, B, intraTotal, intraMax, intraA, intraB, stream);
+    nl += launchSegSort<EpLess>(intraOff, B, intraTotal, intraMax, intraA, intraB, stream);
     const long long quads = (intraTotal + 3) / 4;
     hipLaunchKernelGGL(execution_plan_gather,
                        dim3((unsigned)std::min<long long>(kEpMaxBlocks, (quads + kEpBlock - 1) / kEpBlock)),
-                       dim3(kEpBlock), 0, stream, intraOff, B, intraTotal, intraMax > kEpSortTile ? 1 : 0, 0xffffffffu,
+                       dim3(kEpBlock), 0, stream, intraOff, B, intraTotal, intraMax > kSegSortTile ? 1 : 0, 0xffffffffu,
                        intraA, intraB, intraOut);
     nl++;
   }

@@ -34,6 +34,7 @@
 
 #include "ccmi.h"
 #include "../engine/devtypes.h"
+#include "segments.h"
 
 namespace ccmi {
 
@@ -208,32 +209,11 @@ __global__ __launch_bounds__(kSortBlock) void partition_load_hist(const PlState*
   counts[(size_t)threadIdx.x * tiles + blockIdx.x] = h[threadIdx.x];  // a tile past n writes its zeros
 }
 
-// exclusive scan of counts[0, 256 * tiles) in place: a thread sums a contiguous chunk, the chunk sums are scanned in
-// LDS, the thread writes its chunk's prefixes
+// exclusive scan of counts[0, 256 * tiles) in place
 __global__ __launch_bounds__(kScanBlock) void partition_load_scan(const PlState* __restrict__ st, int slot, int tiles,
                                                                   uint32_t* __restrict__ counts) {
   if ((uint32_t)slot >= st->nPass) return;
-  __shared__ uint32_t s[2][kScanBlock];
-  const int M = 256 * tiles;
-  const int chunk = (M + kScanBlock - 1) / kScanBlock;
-  const int i0 = min(M, (int)threadIdx.x * chunk), i1 = min(M, i0 + chunk);
-  uint32_t sum = 0;
-  for (int i = i0; i < i1; ++i) sum += counts[i];
-  int cur = 0;
-  s[0][threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < kScanBlock; d <<= 1) {
-    const uint32_t v = s[cur][threadIdx.x] + ((int)threadIdx.x >= d ? s[cur][threadIdx.x - d] : 0u);
-    s[cur ^ 1][threadIdx.x] = v;
-    cur ^= 1;
-    __syncthreads();
-  }
-  uint32_t run = s[cur][threadIdx.x] - sum;  // exclusive
-  for (int i = i0; i < i1; ++i) {
-    const uint32_t c = counts[i];
-    counts[i] = run;
-    run += c;
-  }
+  (void)scanCountsInPlace<uint32_t, kScanBlock>(counts, 256 * tiles);
 }
 
 __global__ __launch_bounds__(kSortBlock) void partition_load_scatter(const PlState* __restrict__ st, int slot,

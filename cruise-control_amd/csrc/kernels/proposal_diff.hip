@@ -26,6 +26,7 @@
 #include "ccmi.h"
 #include "../engine/devtypes.h"
 #include "proposal_row.h"
+#include "segments.h"
 
 namespace ccmi {
 
@@ -40,12 +41,6 @@ constexpr int kPdSums = 5;  // inter-broker movements and MB, intra-broker movem
 
 static_assert(sizeof(ccmi_proposal_record) == 160 && sizeof(ccmi_proposal_summary) == 64 && sizeof(PdSums) == 64,
               "record sizes");
-
-__device__ __forceinline__ unsigned long long pdWaveSum(unsigned long long v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += (unsigned long long)__shfl_xor((long long)v, s, 64);
-  return v;
-}
 
 }  // namespace
 
@@ -79,7 +74,7 @@ __global__ __launch_bounds__(kPdBlock) void proposal_diff_flags(PdTables T, int 
         }
       }
     }
-    cnt = (uint32_t)pdWaveSum(cnt);
+    cnt = (uint32_t)waveSum(cnt);
     if (lane == 0) tileCnt[wave] = cnt;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -91,7 +86,7 @@ __global__ __launch_bounds__(kPdBlock) void proposal_diff_flags(PdTables T, int 
   }
   // wave, then workgroup (LDS integer atomics: order-free), then one set of global atomics per workgroup
 #pragma unroll
-  for (int k = 0; k < kPdSums; ++k) acc[k] = pdWaveSum(acc[k]);
+  for (int k = 0; k < kPdSums; ++k) acc[k] = waveSum(acc[k]);
   __syncthreads();  // sh is zeroed (a workgroup without a tile has not passed a barrier yet)
   if (lane == 0)
     for (int k = 0; k < kPdSums; ++k)
@@ -100,33 +95,13 @@ __global__ __launch_bounds__(kPdBlock) void proposal_diff_flags(PdTables T, int 
   if (threadIdx.x < kPdSums && sh[threadIdx.x]) atomicAdd(&sums->v[1 + threadIdx.x], sh[threadIdx.x]);
 }
 
-// exclusive scan of counts[0, tiles) in place, counts[tiles] = sums->v[0] = the total: a thread sums a contiguous chunk,
-// the chunk sums are scanned in LDS, the thread writes its chunk's prefixes
+// exclusive scan of counts[0, tiles) in place, counts[tiles] = sums->v[0] = the total
 __global__ __launch_bounds__(kPdScanBlock) void proposal_diff_scan(int tiles, uint32_t* __restrict__ counts,
                                                                    PdSums* __restrict__ sums) {
-  __shared__ uint32_t s[2][kPdScanBlock];
-  const int chunk = (tiles + kPdScanBlock - 1) / kPdScanBlock;
-  const int i0 = min(tiles, (int)threadIdx.x * chunk), i1 = min(tiles, i0 + chunk);
-  uint32_t sum = 0;
-  for (int i = i0; i < i1; ++i) sum += counts[i];
-  int cur = 0;
-  s[0][threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < kPdScanBlock; d <<= 1) {
-    const uint32_t v = s[cur][threadIdx.x] + ((int)threadIdx.x >= d ? s[cur][threadIdx.x - d] : 0u);
-    s[cur ^ 1][threadIdx.x] = v;
-    cur ^= 1;
-    __syncthreads();
-  }
-  uint32_t run = s[cur][threadIdx.x] - sum;  // exclusive
-  for (int i = i0; i < i1; ++i) {
-    const uint32_t c = counts[i];
-    counts[i] = run;
-    run += c;
-  }
+  const uint32_t total = scanCountsInPlace<uint32_t, kPdScanBlock>(counts, tiles);
   if (threadIdx.x == kPdScanBlock - 1) {
-    counts[tiles] = s[cur][threadIdx.x];
-    sums->v[0] = s[cur][threadIdx.x];
+    counts[tiles] = total;
+    sums->v[0] = total;
   }
 }
 
