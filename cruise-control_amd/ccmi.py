@@ -272,6 +272,50 @@ class PlanSummaryStruct(C.Structure):  # ccmi_plan_summary, 64 bytes
                 ("mingled", C.c_int64), ("reserved", C.c_int64)]
 
 
+class AggregatorConfigStruct(C.Structure):  # ccmi_aggregator_config, 32 bytes
+    _fields_ = [("window_ms", C.c_int64), ("num_windows", C.c_int32), ("min_samples_per_window", C.c_int32),
+                ("num_metrics", C.c_int32), ("num_entities", C.c_int32), ("num_groups", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class AggregatorStateStruct(C.Structure):  # ccmi_aggregator_state, 48 bytes
+    _fields_ = [("generation", C.c_int64), ("oldest_window_index", C.c_int64), ("current_window_index", C.c_int64),
+                ("num_samples", C.c_int64), ("num_present_entities", C.c_int64),
+                ("num_available_windows", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AggregationOptionsStruct(C.Structure):  # ccmi_aggregation_options, 32 bytes
+    _fields_ = [("min_valid_entity_ratio", C.c_double), ("min_valid_entity_group_ratio", C.c_double),
+                ("min_valid_windows", C.c_int32), ("max_allowed_extrapolations_per_entity", C.c_int32),
+                ("granularity", C.c_int32), ("include_invalid_entities", C.c_int32)]
+
+
+class AggregatorCompletenessStruct(C.Structure):  # ccmi_aggregator_completeness, 96 bytes
+    _fields_ = [("generation", C.c_int64), ("num_windows", C.c_int32), ("num_valid_windows", C.c_int32),
+                ("failure", C.c_int32), ("window_capacity", C.c_int32),
+                ("num_interested_entities", C.c_int32), ("num_interested_groups", C.c_int32),
+                ("num_valid_entities", C.c_int32), ("num_valid_groups", C.c_int32),
+                ("valid_entity_ratio", C.c_float), ("valid_entity_group_ratio", C.c_float),
+                ("window_index", C.POINTER(C.c_int64)), ("window_included", C.POINTER(C.c_uint8)),
+                ("valid_entity_ratio_by_window", C.POINTER(C.c_float)),
+                ("valid_entity_ratio_with_group_granularity_by_window", C.POINTER(C.c_float)),
+                ("valid_entity_group_ratio_by_window", C.POINTER(C.c_float)),
+                ("extrapolated_entity_ratio_by_window", C.POINTER(C.c_float))]
+
+
+# ccmi_aggregation_function, ccmi_extrapolation (Extrapolation.java order), ccmi_granularity, ccmi_aggregation_failure
+AGG_AVG, AGG_MAX, AGG_LATEST = range(3)
+EXTRAPOLATIONS = ("NONE", "AVG_AVAILABLE", "AVG_ADJACENT", "FORCED_INSUFFICIENT", "NO_VALID_EXTRAPOLATION")
+GRANULARITY_ENTITY, GRANULARITY_ENTITY_GROUP = 0, 1
+AGG_FAILURE_NONE, AGG_FAILURE_NO_WINDOW_IN_RANGE, AGG_FAILURE_NOT_ENOUGH_VALID_WINDOWS = range(3)
+# KafkaMetricDef's common metrics in id order with their aggregation functions (KafkaMetricDef.java:43-53): the metric
+# set of a partition aggregator, and where the six metrics of ccmi_builder_populate_partition sit in it
+KAFKA_COMMON_METRICS = (("CPU_USAGE", AGG_AVG), ("DISK_USAGE", AGG_LATEST), ("LEADER_BYTES_IN", AGG_AVG),
+                        ("LEADER_BYTES_OUT", AGG_AVG), ("PRODUCE_RATE", AGG_AVG), ("FETCH_RATE", AGG_AVG),
+                        ("MESSAGE_IN_RATE", AGG_AVG), ("REPLICATION_BYTES_IN_RATE", AGG_AVG),
+                        ("REPLICATION_BYTES_OUT_RATE", AGG_AVG))
+
+
 # CCMI_SEL_* (ReplicaSortFunctionFactory's selection functions) and CCMI_PRIO_* (its priority functions)
 SEL_LEADERS, SEL_FOLLOWERS, SEL_ONLINE, SEL_OFFLINE, SEL_IMMIGRANTS, SEL_IMMIGRANT_OR_OFFLINE = 1, 2, 4, 8, 16, 32
 SORT_PRIORITIES = ("offline", "immigrants")  # index = CCMI_PRIO_*
@@ -328,7 +372,10 @@ EXPORTED_SYMBOLS = (
     "ccmi_topic_broker_set",
     "ccmi_builder_create", "ccmi_builder_destroy", "ccmi_builder_create_broker", "ccmi_builder_add_disk",
     "ccmi_builder_populate_partition", "ccmi_builder_set_broker_state", "ccmi_builder_set_disk_state",
-    "ccmi_builder_desc", "ccmi_builder_broker_ids")
+    "ccmi_builder_desc", "ccmi_builder_broker_ids",
+    "ccmi_aggregator_create", "ccmi_aggregator_destroy", "ccmi_aggregator_add_samples", "ccmi_aggregator_state_query",
+    "ccmi_aggregator_completeness_query", "ccmi_aggregator_aggregate", "ccmi_aggregator_peek_current_window",
+    "ccmi_aggregator_remove_entities", "ccmi_aggregator_clear")
 
 # int (*)(void* ctx, int64_t* key): replace *key by the MIN over all shards, return 0 (include/ccmi.h)
 AllreduceMinFn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int64))
@@ -403,6 +450,28 @@ class Library:
                                               C.POINTER(PlanSummaryStruct), C.c_void_p, C.c_int64, C.c_void_p,
                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                               C.c_void_p, C.c_int64]
+        # MetricSampleAggregator on the device: all nine symbols or none
+        self.has_aggregator = hasattr(L, "ccmi_aggregator_create")
+        if self.has_aggregator:
+            L.ccmi_aggregator_create.argtypes = [C.c_int32, C.POINTER(AggregatorConfigStruct), C.c_void_p, C.c_void_p,
+                                                 C.POINTER(C.c_void_p)]
+            L.ccmi_aggregator_destroy.argtypes = [C.c_void_p]
+            L.ccmi_aggregator_destroy.restype = None
+            L.ccmi_aggregator_add_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                      C.c_void_p, C.POINTER(C.c_int64)]
+            L.ccmi_aggregator_state_query.argtypes = [C.c_void_p, C.POINTER(AggregatorStateStruct)]
+            L.ccmi_aggregator_completeness_query.argtypes = [C.c_void_p, C.c_int64, C.c_int64,
+                                                             C.POINTER(AggregationOptionsStruct), C.c_void_p,
+                                                             C.POINTER(AggregatorCompletenessStruct), C.c_void_p,
+                                                             C.c_void_p]
+            L.ccmi_aggregator_aggregate.argtypes = [C.c_void_p, C.c_int64, C.c_int64,
+                                                    C.POINTER(AggregationOptionsStruct), C.c_void_p,
+                                                    C.POINTER(AggregatorCompletenessStruct), C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+            L.ccmi_aggregator_peek_current_window.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                              C.POINTER(C.c_int64)]
+            L.ccmi_aggregator_remove_entities.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+            L.ccmi_aggregator_clear.argtypes = [C.c_void_p]
         L.ccmi_session_apply.argtypes = [C.c_void_p, C.POINTER(ActionStruct), C.c_int64, C.POINTER(C.c_int64)]
         # additive at ABI v13: the symbol's presence is the capability flag (also of goal kind 24)
         self.has_remove_disks = hasattr(L, "ccmi_session_mark_disks_for_removal")
@@ -1496,6 +1565,224 @@ class LoadMonitorModel:
         W = d.num_windows
         return [[[d.replica_load[(r * 6 + m) * W + w] for w in range(W)] for m in range(6)]
                 for r in range(d.num_replicas)]
+
+
+@dataclass
+class AggregationOptions:
+    """monitor/sampling/aggregator/AggregationOptions.java without the interested entities (a mask of the calls)."""
+    min_valid_entity_ratio: float = 0.0
+    min_valid_entity_group_ratio: float = 0.0
+    min_valid_windows: int = 1
+    max_allowed_extrapolations_per_entity: int = 5
+    granularity: int = GRANULARITY_ENTITY
+    include_invalid_entities: bool = False
+
+    def struct(self) -> AggregationOptionsStruct:
+        return AggregationOptionsStruct(float(self.min_valid_entity_ratio), float(self.min_valid_entity_group_ratio),
+                                        int(self.min_valid_windows), int(self.max_allowed_extrapolations_per_entity),
+                                        int(self.granularity), 1 if self.include_invalid_entities else 0)
+
+
+class AggregatorCompleteness:
+    """MetricSampleCompleteness as ccmi_aggregator_completeness returns it: numpy arrays over the walked windows, newest
+    first (`windows` holds their indices, `included` which of them are valid window indices), the totals, the two
+    overall float ratios, and `failure` (AGG_FAILURE_*, set by aggregate only)."""
+
+    def __init__(self, np, s: AggregatorCompletenessStruct, arrays, valid_entities=None, valid_groups=None):
+        n = s.num_windows
+        self.generation = s.generation
+        self.failure = s.failure
+        self.windows, self.included = arrays[0][:n].copy(), arrays[1][:n].copy()
+        self.valid_entity_ratio_by_window = arrays[2][:n].copy()
+        self.valid_entity_ratio_with_group_granularity_by_window = arrays[3][:n].copy()
+        self.valid_entity_group_ratio_by_window = arrays[4][:n].copy()
+        self.extrapolated_entity_ratio_by_window = arrays[5][:n].copy()
+        self.valid_window_indices = self.windows[self.included != 0]
+        self.num_interested_entities, self.num_interested_groups = s.num_interested_entities, s.num_interested_groups
+        self.num_valid_entities, self.num_valid_groups = s.num_valid_entities, s.num_valid_groups
+        self.valid_entity_ratio = np.float32(s.valid_entity_ratio)
+        self.valid_entity_group_ratio = np.float32(s.valid_entity_group_ratio)
+        self.valid_entities, self.valid_groups = valid_entities, valid_groups  # uint8 masks, completeness() only
+
+
+class AggregationResult:
+    """MetricSampleAggregationResult: `entities` (ascending ids, the first `capacity` of `num_entities`), `values`
+    float32 [k][M][Wv] and `extrapolations` uint8 [k][Wv] over the valid windows newest first, `invalid` uint8 [k]."""
+
+    def __init__(self, completeness, num_entities, entities, values, extrapolations, invalid):
+        self.completeness, self.num_entities = completeness, num_entities
+        self.entities, self.values, self.extrapolations, self.invalid = entities, values, extrapolations, invalid
+
+    def leader_metrics(self, row: int):
+        """Row `row` of an aggregate over KAFKA_COMMON_METRICS as ccmi_builder_populate_partition's leader_metrics:
+        [6 * Wv] floats in ccmi_metric order, newest window first."""
+        import numpy as np
+
+        if self.values.shape[1] != len(KAFKA_COMMON_METRICS):
+            raise IllegalArgumentException("the aggregator's metrics are not KafkaMetricDef's common metrics")
+        names = [n for n, _ in KAFKA_COMMON_METRICS]
+        pick = [names.index(m) for m in LoadMonitorModel.METRICS]
+        return np.ascontiguousarray(self.values[row][pick], dtype=np.float32).reshape(-1)
+
+    def populate_partition(self, model: "LoadMonitorModel", row: int, topic: str, partition: int,
+                           replicas: Sequence[int], leader: Optional[int], **kwargs) -> None:
+        """LoadMonitorModel.populate_partition with the aggregated leader metrics of row `row`."""
+        wv = self.values.shape[2]
+        flat = self.leader_metrics(row)
+        model.populate_partition(topic, partition, replicas, leader,
+                                 {m: flat[i * wv:(i + 1) * wv] for i, m in enumerate(LoadMonitorModel.METRICS)},
+                                 **kwargs)
+
+
+class MetricSampleAggregator:
+    """MetricSampleAggregator on the device (ccmi_aggregator_*): the step before LoadMonitorModel. Entities are dense ids
+    with a group each (for partitions the topic); metric m has metric_functions[m] (AGG_AVG / AGG_MAX / AGG_LATEST).
+
+        agg = MetricSampleAggregator(5, 300_000, 4, [f for _, f in KAFKA_COMMON_METRICS], topic_of_partition)
+        agg.add_samples(partition_ids, times_ms, values)          # values: [n][M] doubles
+        res = agg.aggregate(-1, now_ms, AggregationOptions(0.95, 0.0, 1, 5, GRANULARITY_ENTITY_GROUP, True))
+        res.populate_partition(model, row, topic, partition, replicas, leader)
+    """
+
+    def __init__(self, num_windows: int, window_ms: int, min_samples_per_window: int,
+                 metric_functions: Sequence[int], entity_group: Sequence[int], num_groups: Optional[int] = None,
+                 device: int = 0, lib: Optional[Library] = None):
+        import numpy as np
+
+        self.lib = lib or Library.get()
+        self.handle = None
+        if not self.lib.has_aggregator:
+            raise UnsupportedOperationException(f"{self.lib.path} does not export ccmi_aggregator_create: the "
+                                                "aggregator runs on the device only")
+        fn = np.ascontiguousarray(metric_functions, dtype=np.uint8)
+        grp = np.ascontiguousarray(entity_group, dtype=np.int32)
+        self.num_windows, self.window_ms, self.min_samples_per_window = num_windows, window_ms, min_samples_per_window
+        self.M, self.E = int(fn.size), int(grp.size)
+        self.G = int(num_groups) if num_groups is not None else (int(grp.max()) + 1 if grp.size else 0)
+        cfg = AggregatorConfigStruct(window_ms, num_windows, min_samples_per_window, self.M, self.E, self.G, 0)
+        h = C.c_void_p()
+        self.lib.check(self.lib.lib.ccmi_aggregator_create(device, C.byref(cfg), fn.ctypes.data, grp.ctypes.data,
+                                                           C.byref(h)))
+        self.handle = h
+
+    def __del__(self):
+        try:
+            if self.handle:
+                self.lib.lib.ccmi_aggregator_destroy(self.handle)
+        except Exception:
+            pass
+
+    def add_samples(self, entities, times_ms, values):
+        """MetricSampleAggregator.addSample for every sample in order; -> uint8 accepted flags."""
+        import numpy as np
+
+        ent = np.ascontiguousarray(entities, dtype=np.int32).reshape(-1)
+        tms = np.ascontiguousarray(times_ms, dtype=np.int64).reshape(-1)
+        val = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        n = int(ent.size)
+        if tms.size != n or val.size != n * self.M:
+            raise IllegalArgumentException("entities, times_ms and values disagree on the number of samples")
+        accepted = np.zeros(n, dtype=np.uint8)
+        num = C.c_int64(0)
+        self.lib.check(self.lib.lib.ccmi_aggregator_add_samples(self.handle, ent.ctypes.data, tms.ctypes.data,
+                                                                val.ctypes.data, n, accepted.ctypes.data, C.byref(num)))
+        return accepted
+
+    def state(self) -> AggregatorStateStruct:
+        s = AggregatorStateStruct()
+        self.lib.check(self.lib.lib.ccmi_aggregator_state_query(self.handle, C.byref(s)))
+        return s
+
+    generation = property(lambda self: self.state().generation)
+    oldest_window_index = property(lambda self: self.state().oldest_window_index)
+    current_window_index = property(lambda self: self.state().current_window_index)
+    num_samples = property(lambda self: self.state().num_samples)
+    num_available_windows = property(lambda self: self.state().num_available_windows)
+    num_present_entities = property(lambda self: self.state().num_present_entities)
+
+    def _completeness_struct(self, np):
+        cap = self.num_windows + 1
+        arrays = [np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.uint8)] + \
+                 [np.zeros(cap, dtype=np.float32) for _ in range(4)]
+        s = AggregatorCompletenessStruct()
+        s.window_capacity = cap
+        s.window_index = arrays[0].ctypes.data_as(C.POINTER(C.c_int64))
+        s.window_included = arrays[1].ctypes.data_as(C.POINTER(C.c_uint8))
+        s.valid_entity_ratio_by_window = arrays[2].ctypes.data_as(C.POINTER(C.c_float))
+        s.valid_entity_ratio_with_group_granularity_by_window = arrays[3].ctypes.data_as(C.POINTER(C.c_float))
+        s.valid_entity_group_ratio_by_window = arrays[4].ctypes.data_as(C.POINTER(C.c_float))
+        s.extrapolated_entity_ratio_by_window = arrays[5].ctypes.data_as(C.POINTER(C.c_float))
+        return s, arrays
+
+    def _mask(self, np, interested):
+        if interested is None:
+            return None
+        m = np.ascontiguousarray(interested, dtype=np.uint8).reshape(-1)
+        if m.size != self.E:
+            raise IllegalArgumentException("the interested mask has one byte per entity")
+        return m
+
+    def completeness(self, from_ms: int, to_ms: int, options: AggregationOptions, interested=None,
+                     masks: bool = True) -> AggregatorCompleteness:
+        """MetricSampleAggregator.completeness; `interested` is a byte mask over the entities (None, or nothing
+        selected: every present entity). With `masks` the valid entities and groups come back as uint8 masks."""
+        import numpy as np
+
+        s, arrays = self._completeness_struct(np)
+        mask = self._mask(np, interested)
+        ve = np.zeros(self.E, dtype=np.uint8) if masks else None
+        vg = np.zeros(self.G, dtype=np.uint8) if masks else None
+        o = options.struct()
+        self.lib.check(self.lib.lib.ccmi_aggregator_completeness_query(
+            self.handle, from_ms, to_ms, C.byref(o), mask.ctypes.data if mask is not None else None, C.byref(s),
+            ve.ctypes.data if masks else None, vg.ctypes.data if masks else None))
+        return AggregatorCompleteness(np, s, arrays, ve, vg)
+
+    def aggregate(self, from_ms: int, to_ms: int, options: AggregationOptions, interested=None,
+                  capacity: Optional[int] = None) -> AggregationResult:
+        """MetricSampleAggregator.aggregate. NotEnoughValidWindowsException is an expected outcome: the result then has
+        completeness.failure set and no rows. `capacity` cuts the rows (num_entities is always the full count)."""
+        import numpy as np
+
+        s, arrays = self._completeness_struct(np)
+        mask = self._mask(np, interested)
+        cap = self.E if capacity is None else int(capacity)
+        wmax = self.num_windows
+        ent = np.zeros(cap, dtype=np.int32)
+        val = np.zeros(cap * self.M * wmax, dtype=np.float32)
+        ext = np.zeros(cap * wmax, dtype=np.uint8)
+        inv = np.zeros(cap, dtype=np.uint8)
+        n = C.c_int64(0)
+        o = options.struct()
+        self.lib.check(self.lib.lib.ccmi_aggregator_aggregate(
+            self.handle, from_ms, to_ms, C.byref(o), mask.ctypes.data if mask is not None else None, C.byref(s),
+            ent.ctypes.data, val.ctypes.data, ext.ctypes.data, inv.ctypes.data, cap, C.byref(n)))
+        k, wv = min(cap, n.value), s.num_valid_windows
+        return AggregationResult(AggregatorCompleteness(np, s, arrays), int(n.value), ent[:k],
+                                 val[:k * self.M * wv].reshape(k, self.M, wv), ext[:k * wv].reshape(k, wv), inv[:k])
+
+    def peek_current_window(self, capacity: Optional[int] = None):
+        """peekCurrentWindow: -> (entities ascending, values float32 [k][M], extrapolations uint8 [k], num_entities)."""
+        import numpy as np
+
+        cap = self.E if capacity is None else int(capacity)
+        ent = np.zeros(cap, dtype=np.int32)
+        val = np.zeros(cap * self.M, dtype=np.float32)
+        ext = np.zeros(cap, dtype=np.uint8)
+        n = C.c_int64(0)
+        self.lib.check(self.lib.lib.ccmi_aggregator_peek_current_window(self.handle, ent.ctypes.data, val.ctypes.data,
+                                                                        ext.ctypes.data, cap, C.byref(n)))
+        k = min(cap, n.value)
+        return ent[:k], val[:k * self.M].reshape(k, self.M), ext[:k], int(n.value)
+
+    def remove_entities(self, entities) -> None:
+        import numpy as np
+
+        ids = np.ascontiguousarray(entities, dtype=np.int32).reshape(-1)
+        self.lib.check(self.lib.lib.ccmi_aggregator_remove_entities(self.handle, ids.ctypes.data, int(ids.size)))
+
+    def clear(self) -> None:
+        self.lib.check(self.lib.lib.ccmi_aggregator_clear(self.handle))
 
 
 class ClusterModel:

@@ -549,4 +549,44 @@ struct StatsOut {
   int32_t topicMax, topicMin;
 };
 
+// ccmi_aggregator (kernels/aggregator.hip, K17): MetricSampleAggregator on the device. The state is entity-minor so a
+// wave touches consecutive addresses: counts[a][e], values[a][m][e] for array index a of the cyclic buffer of L =
+// num_windows + 1 windows, and one validity and one extrapolation word per entity (bit a). The entity passes are
+// grid-stride loops of kAggBlock lanes over at most kAggMaxBlocks workgroups; the compaction of an aggregate's covered
+// entities takes tiles of kAggTile consecutive entities per workgroup.
+constexpr int kAggBlock = 256;      // 4 waves
+constexpr int kAggMaxBlocks = 256;  // workgroups of a grid-stride pass: 65536 lanes
+constexpr int kAggTile = 1024;      // entities per compaction tile, a multiple of kAggBlock
+static_assert(kAggTile % kAggBlock == 0, "kAggTile");
+struct AggTables {
+  uint8_t* counts;       // [L][E]
+  float* values;         // [L][M][E]
+  uint32_t* valid;       // [E] _validity
+  uint32_t* extrap;      // [E] _extrapolations
+  uint8_t* present;      // [E] a key of _rawMetrics
+  const int32_t* group;  // [E]
+  const uint8_t* fn;     // [M] ccmi_aggregation_function
+  int32_t E, G, M, L, minSamples, halfMin;
+};
+// One maybeRollOutNewWindow of a batch that reset windows: it happens before the sample at batch position pos.
+struct AggRollEvent {
+  long long pos, newOldest, prevOldest;
+  int32_t numReset, pad;
+};
+// The scratch of one completeness walk. ctr: kAggCtrHead words, then kAggCtrPerWindow per walked window (newest first).
+enum : int { kAcTotalE = 0, kAcTotalG, kAcIncluded, kAcValidE, kAcValidG, kAcCovered, kAggCtrHead = 8 };
+enum : int { kAwValid = 0, kAwExtrap, kAwGroups, kAwGroupGran, kAwMergeE, kAwMergeG, kAwIncluded, kAggCtrPerWindow = 8 };
+struct AggWalk {
+  uint8_t* inter;       // [E] interested
+  uint8_t* ginter;      // [G] a group of an interested entity
+  uint8_t* validE;      // [E] MetricSampleCompleteness._validEntities
+  uint8_t* validG;      // [G] _validEntityGroups
+  uint8_t* vfw;         // [E] validEntitiesForWindow of the window being walked
+  uint8_t* gValidW;     // [G] validGroupsForWindow
+  int32_t* extrapCnt;   // [E] includedEntityExtrapolations
+  uint32_t* gValidCnt;  // [windows][G] numValidEntitiesByGroupForOption
+  uint8_t* gInvalid;    // [windows][G] invalidGroupsForOption
+  unsigned long long* ctr;
+};
+
 }  // namespace ccmi

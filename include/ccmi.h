@@ -39,6 +39,9 @@
  *   ccmi_execution_plan        <- ExecutionTaskPlanner.addExecutionProposals  executor/ExecutionTaskPlanner.java:137-273,
  *                                 brokerComparator :518-539, strategy/AbstractReplicaMovementStrategy.java:28-85 (the
  *                                 tasks, their ids, the per-broker task sets in strategy order, the broker order)
+ *   ccmi_aggregator_*          <- MetricSampleAggregator.addSample / completeness / aggregate / peekCurrentWindow
+ *                                 cruise-control-core monitor/sampling/aggregator/MetricSampleAggregator.java:141-293,
+ *                                 RawMetricValues.java, WindowState.java (the step before ccmi_builder_populate_partition)
  *   ccmi_random_cluster        <- test fixture RandomCluster.generate+populate
  *                                 (src/test/java/.../model/RandomCluster.java:53-455)
  *
@@ -937,6 +940,123 @@ ccmi_status ccmi_execution_plan(ccmi_session* s, const ccmi_execution_plan_query
                                 int64_t* intra_offsets /* [B + 1] */, int32_t* intra_entries /* [intra_capacity] */,
                                 int64_t intra_capacity, int32_t* leader_tasks /* [leader_capacity] */,
                                 int64_t leader_capacity);
+
+/*
+ * ccmi_aggregator_*, additive at ABI v13: the capability flag is the presence of the symbols, ccmi_perf_counters keeps
+ * its layout. MetricSampleAggregator on the device: the step of LoadMonitor.clusterModel that turns metric samples into
+ * the per-window floats ccmi_builder_populate_partition takes as leader_metrics. A literal restatement of
+ * cruise-control-core monitor/sampling/aggregator/{MetricSampleAggregator, RawMetricValues, WindowState,
+ * MetricSampleAggregatorState.computeCompleteness, MetricSampleCompleteness, AggregationOptions, Extrapolation}.java and
+ * common/WindowIndexedArrays.java. An aggregator owns its buffers and its stream on one device and needs no session;
+ * it is single-threaded, several may live on one device.
+ *
+ * Entities are the dense ids 0..E-1 with entity_group[e] in 0..G-1 (for partitions the topic; the ids of a group need
+ * not be contiguous). Metrics are 0..M-1, each with a ccmi_aggregation_function. An entity is "present" (a key of
+ * _rawMetrics) from its first accepted sample until ccmi_aggregator_remove_entities or ccmi_aggregator_clear.
+ *
+ * ccmi_aggregator_add_samples has the effect of MetricSampleAggregator.addSample on the n samples in batch order:
+ * windowIndex = time / window_ms + 1, a sample older than the oldest window is dropped (accepted[i] = 0),
+ * maybeRollOutNewWindow (leaps larger than the windows kept and several roll-outs inside one batch included), the
+ * updateOldestWindowIndex of a new RawMetricValues, counts and values by add / max / latest with their (float) of a
+ * double expression, the _validity and _extrapolations bits by the reference's state machine, and the generation
+ * (newWindowsRolledOut || windowIndex != _currentWindowIndex). Two samples of one entity take effect in batch order.
+ * _counts is a Java byte: more than 127 samples in one window of one entity is outside the contract (the count then
+ * differs from the reference's wrapped byte), as is min_samples_per_window outside 1..127. A negative sample time is
+ * refused (CCMI_E_INVALID) before anything changes, and num_windows is at most 31 (one validity bit per kept window).
+ *
+ * ccmi_aggregator_completeness: MetricSampleAggregator.completeness. `interested` is a byte mask over the E entities;
+ * NULL, or a mask selecting nothing, means every present entity (interpretAggregationOptions on an empty set). The
+ * windows of the clamped range are walked newest to oldest through WindowState.maybeInclude; per walked window the four
+ * ratios of fillInValidRatios and whether it was included, newest first, in the arrays the caller hangs into the
+ * struct (window_capacity of each; num_windows + 1 always suffices; CCMI_E_INVALID when too small). A ratio over no
+ * interested entity is Java's canonical NaN. The reference caches window states by generation and completeness by
+ * options; this always computes from the current bits, which is the reference's answer whenever its caches are current.
+ *
+ * ccmi_aggregator_aggregate: completeness, validateCompleteness, then RawMetricValues.aggregate over the valid windows,
+ * newest first, for include_invalid_entities ? the interested entities : the valid ones, in ascending id order, cut to
+ * `capacity`; *num_entities is always the full count, so capacity = 0 is the sizing call and rows beyond the count stay
+ * untouched. values is [k][M][Wv] and extrapolations [k][Wv] with Wv = out->num_valid_windows; an entity that is not
+ * present gets zeros and CCMI_EXTRAPOLATION_NO_VALID in every window and is invalid, a present one is invalid iff
+ * !isValid(max_allowed_extrapolations_per_entity). NotEnoughValidWindowsException is an expected outcome: CCMI_OK with
+ * out->failure set, *num_entities = 0 and no row written. The two coverage IllegalStateExceptions are CCMI_E_STATE with
+ * the reference's message text (its options suffix left out) in ccmi_last_error; they are restated for completeness
+ * and not reachable, since a window is included only if the merged ratios meet both minima and the final ratios are
+ * those of the last included window.
+ *
+ * ccmi_aggregator_peek_current_window: peekCurrentWindow, one window (the aggregator's current one, no range check)
+ * for every present entity, ascending ids, values [k][M], the same capacity convention.
+ * ccmi_aggregator_remove_entities: removeEntities (the generation advances once if any was present).
+ * ccmi_aggregator_clear: clear (the window indices stay, as in the reference).
+ *
+ * Errors: CCMI_E_INVALID for a NULL argument that is not marked nullable, num_windows < 1 or > 31, window_ms < 1,
+ * min_samples_per_window outside 1..127, M < 1, E < 1, G < 1, a group or function id out of range, n < 0, an entity id
+ * out of range, a negative sample time, min_valid_windows < 1, a granularity outside the enum, capacity < 0;
+ * CCMI_E_DEVICE for a device failure. On error the outputs are unspecified.
+ */
+typedef enum ccmi_aggregation_function { CCMI_AGG_AVG = 0, CCMI_AGG_MAX = 1, CCMI_AGG_LATEST = 2 } ccmi_aggregation_function;
+typedef enum ccmi_extrapolation {
+  CCMI_EXTRAPOLATION_NONE = 0,
+  CCMI_EXTRAPOLATION_AVG_AVAILABLE = 1,
+  CCMI_EXTRAPOLATION_AVG_ADJACENT = 2,
+  CCMI_EXTRAPOLATION_FORCED_INSUFFICIENT = 3,
+  CCMI_EXTRAPOLATION_NO_VALID = 4
+} ccmi_extrapolation;
+typedef enum ccmi_granularity { CCMI_GRANULARITY_ENTITY = 0, CCMI_GRANULARITY_ENTITY_GROUP = 1 } ccmi_granularity;
+typedef enum ccmi_aggregation_failure {
+  CCMI_AGG_FAILURE_NONE = 0,
+  CCMI_AGG_FAILURE_NO_WINDOW_IN_RANGE = 1,         /* "There is no window available in range ..." */
+  CCMI_AGG_FAILURE_NOT_ENOUGH_VALID_WINDOWS = 2    /* "There are only %d valid windows ..." */
+} ccmi_aggregation_failure;
+
+typedef struct ccmi_aggregator ccmi_aggregator;
+typedef struct ccmi_aggregator_config {
+  int64_t window_ms;
+  int32_t num_windows, min_samples_per_window, num_metrics, num_entities, num_groups, reserved;
+} ccmi_aggregator_config;
+typedef struct ccmi_aggregator_state {
+  int64_t generation, oldest_window_index, current_window_index, num_samples, num_present_entities;
+  int32_t num_available_windows, reserved;
+} ccmi_aggregator_state;
+typedef struct ccmi_aggregation_options {
+  double min_valid_entity_ratio, min_valid_entity_group_ratio;
+  int32_t min_valid_windows, max_allowed_extrapolations_per_entity, granularity, include_invalid_entities;
+} ccmi_aggregation_options;
+typedef struct ccmi_aggregator_completeness {
+  int64_t generation;
+  int32_t num_windows, num_valid_windows, failure, window_capacity;
+  int32_t num_interested_entities, num_interested_groups, num_valid_entities, num_valid_groups;
+  float valid_entity_ratio, valid_entity_group_ratio;
+  int64_t* window_index;                                  /* [window_capacity] the walked windows, newest first */
+  uint8_t* window_included;                               /* [window_capacity] 1 = a valid window index */
+  float* valid_entity_ratio_by_window;                    /* [window_capacity] */
+  float* valid_entity_ratio_with_group_granularity_by_window;
+  float* valid_entity_group_ratio_by_window;
+  float* extrapolated_entity_ratio_by_window;
+} ccmi_aggregator_completeness;
+
+ccmi_status ccmi_aggregator_create(int32_t device_ordinal, const ccmi_aggregator_config* config,
+                                   const uint8_t* metric_function /* [M] */, const int32_t* entity_group /* [E] */,
+                                   ccmi_aggregator** out);
+void ccmi_aggregator_destroy(ccmi_aggregator* a);
+ccmi_status ccmi_aggregator_add_samples(ccmi_aggregator* a, const int32_t* entity /* [n] */,
+                                        const int64_t* time_ms /* [n] */, const double* values /* [n][M] */, int64_t n,
+                                        uint8_t* accepted /* nullable [n] */, int64_t* num_accepted /* nullable */);
+ccmi_status ccmi_aggregator_state_query(ccmi_aggregator* a, ccmi_aggregator_state* out);
+ccmi_status ccmi_aggregator_completeness_query(ccmi_aggregator* a, int64_t from_ms, int64_t to_ms,
+                                               const ccmi_aggregation_options* options,
+                                               const uint8_t* interested /* nullable [E] */,
+                                               ccmi_aggregator_completeness* out, uint8_t* valid_entities /* nullable [E] */,
+                                               uint8_t* valid_groups /* nullable [G] */);
+ccmi_status ccmi_aggregator_aggregate(ccmi_aggregator* a, int64_t from_ms, int64_t to_ms,
+                                      const ccmi_aggregation_options* options, const uint8_t* interested /* nullable [E] */,
+                                      ccmi_aggregator_completeness* out, int32_t* entities /* [capacity] */,
+                                      float* values /* [capacity][M][Wv] */, uint8_t* extrapolations /* [capacity][Wv] */,
+                                      uint8_t* invalid /* [capacity] */, int64_t capacity, int64_t* num_entities);
+ccmi_status ccmi_aggregator_peek_current_window(ccmi_aggregator* a, int32_t* entities /* [capacity] */,
+                                                float* values /* [capacity][M] */, uint8_t* extrapolations /* [capacity] */,
+                                                int64_t capacity, int64_t* num_entities);
+ccmi_status ccmi_aggregator_remove_entities(ccmi_aggregator* a, const int32_t* entities /* [n] */, int64_t n);
+ccmi_status ccmi_aggregator_clear(ccmi_aggregator* a);
 
 /*
  * Destination-sharded mode (one process per GPU): every rank creates a session on its own device from the same
