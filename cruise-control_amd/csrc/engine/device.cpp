@@ -103,6 +103,15 @@ int Device::countGfx950() {
 
 Device::Device(int ordinal, int B, int R, int P, int T, int maxGoalSlots)
     : ordinal_(ordinal), B_(B), R_(R), P_(P), T_(T), ldB_((B + 3) & ~3), G_(maxGoalSlots) {
+  // this Device has the queue scans' keyed membership table (device.h KeyedOps)
+  keyedOps_.bind = [](Device& d, uint64_t key, int stride) { return d.kqBindImpl(key, stride); };
+  keyedOps_.writeRow = [](Device& d, int b, int slot, int r, uint64_t key) { d.kqWriteRowImpl(b, slot, r, key); };
+  keyedOps_.setLen = [](Device& d, int b, int len) { d.kqSetLenImpl(b, len); };
+  keyedOps_.scan = [](Device& d, const DevProgram& prog, const KeyedMirror& mir, int head, bool hasSkip, uint64_t skipKey,
+                      const int32_t* tail, int nTail, const int32_t* cands, int N) {
+    if (!d.kqKey_ || mir.stride() != d.kqStride_) throw std::logic_error("scanQueueKeyed before kqBind");
+    return d.scanQueueImpl(prog, &mir, head, hasSkip ? 1 : 0, skipKey, tail, nTail, cands, N);
+  };
   int n = 0;
   hipCheck(hipGetDeviceCount(&n), "hipGetDeviceCount");
   if (ordinal < 0 || ordinal >= n) throw std::runtime_error("no HIP device with ordinal " + std::to_string(ordinal));
@@ -289,6 +298,7 @@ Device::~Device() {
   if (fg_) (void)hipFree(fg_);
   if (segPool_) (void)hipFree(segPool_);
   if (qdir_) (void)hipFree(qdir_);
+  if (kqMem_) (void)hipFree(kqMem_);
   if (dServerT0_) (void)hipFree(dServerT0_);
   if (dAccept_) (void)hipFree(dAccept_);
   for (void* p : statsRowAllocs_)  // brokerStats (device_accept.cpp)
@@ -1525,14 +1535,60 @@ bool Device::qdirSetMany(const std::vector<int32_t>& bs,
   return true;
 }
 
+bool Device::kqBindImpl(uint64_t key, int stride) {
+  if (stride <= 0 || stride >= (1 << 20)) return false;
+  const size_t lenBytes = ((size_t)B_ * 4 + 255) & ~(size_t)255;
+  const size_t bytes = lenBytes + (size_t)B_ * (size_t)stride * sizeof(KeyedRow);
+  if (bytes > ((size_t)2 << 30)) return false;
+  if (bytes > kqBytes_) {
+    DeviceGuard dg(ordinal_);
+    stopServer();  // no command reads the old block any more
+    if (kqMem_) (void)hipFree(kqMem_);
+    kqMem_ = nullptr;
+    kqBytes_ = 0;
+    kqKey_ = 0;
+    if (hipExtMallocWithFlags((void**)&kqMem_, bytes, hipDeviceMallocFinegrained) != hipSuccess) {
+      (void)hipGetLastError();
+      kqMem_ = nullptr;
+      return false;
+    }
+    kqBytes_ = bytes;
+  }
+  kqLens_ = reinterpret_cast<int32_t*>(kqMem_);
+  kqRows_ = reinterpret_cast<KeyedRow*>(kqMem_ + lenBytes);
+  kqStride_ = stride;
+  kqKey_ = key;
+  std::memset(kqLens_, 0, (size_t)B_ * 4);
+  return true;
+}
+
+void Device::kqWriteRowImpl(int b, int slot, int r, uint64_t key) {
+  const int p = rowPart_[r];
+  const KeyedRow row{key, r, p, partTopic_[p], 0};
+  std::memcpy(&kqRows_[(size_t)b * (size_t)kqStride_ + (size_t)slot], &row, sizeof(row));
+}
+
+void Device::kqSetLenImpl(int b, int len) { *reinterpret_cast<volatile int32_t*>(&kqLens_[b]) = len; }
+
 int64_t Device::scanQueue(const DevProgram& prog, int head, int skip0, const int32_t* tail, int nTail,
                           const int32_t* cands, int N) {
+  return scanQueueImpl(prog, nullptr, head, skip0, 0, tail, nTail, cands, N);
+}
+
+int64_t Device::scanQueueImpl(const DevProgram& prog, const KeyedMirror* mir, int head, int skip0, uint64_t skipKey,
+                              const int32_t* tail, int nTail, const int32_t* cands, int N) {
   DeviceGuard dg(ordinal_);
   const int hasHead = head >= 0 ? 1 : 0;
   const int n = hasHead + nTail;
   if (n <= 0 || N <= 0) return -1;
   auto entry = [&](int i) { return i < hasHead ? head : tail[i - hasHead]; };
-  const int span = qdirSpan_;
+  const int span = mir ? kqStride_ : qdirSpan_;
+  // the leading rows (in sort order) of entry i the scan passes over: the head entry's continuation
+  auto skipped = [&](int i) {
+    if (i != 0 || !skip0) return 0;
+    return mir ? mir->below(entry(0), skipKey + 1) : skip0;
+  };
+  auto lenOf = [&](int i) { return mir ? mir->len(entry(i)) : qdirLen(entry(i)); };
   const uint64_t space = (uint64_t)n * (uint64_t)span * (uint64_t)N;
   if (queueUsable() && space < (1ull << 31)) {
     bool serve = false;
@@ -1578,7 +1634,10 @@ int64_t Device::scanQueue(const DevProgram& prog, int head, int skip0, const int
         c.oT = (uint32_t)(oRows + g.otd);
         c.oA = (uint32_t)oA;
         c.oC = (uint32_t)oC;
-        c.queueDir = (unsigned long long)(uintptr_t)qdir_;
+        c.queueDir = (unsigned long long)(uintptr_t)(mir ? (void*)kqLens_ : (void*)qdir_);
+        c.queueStride = mir ? kqStride_ : 0;
+        c.queueRows = (unsigned long long)(uintptr_t)kqRows_;
+        c.skipKey = skipKey;
         const auto tq = std::chrono::steady_clock::now();
         if (postCommand(c, (g.nb | g.nr | g.np | g.nt) != 0)) {
           perf.serverScans++;
@@ -1596,10 +1655,12 @@ int64_t Device::scanQueue(const DevProgram& prog, int head, int skip0, const int
           int64_t required = 0, K = 0;
           const int wi = key < 0 ? n : (int)(key / N / span);
           for (int i = 0; i < wi; ++i) {
-            const int len = qdirLen(entry(i)), s0 = i == 0 ? skip0 : 0;
+            const int len = lenOf(i), s0 = skipped(i);
             required += len > s0 ? (int64_t)(len - s0) * N : 0;
           }
-          if (key >= 0) required += ((key / N) % span - (wi == 0 ? skip0 : 0)) * N + key % N + 1;
+          if (key >= 0 && mir)  // every row of the winner's entry is evaluated: its minimum is known only then
+            required += (int64_t)(lenOf(wi) - skipped(wi)) * N;
+          else if (key >= 0) required += ((key / N) % span - (wi == 0 ? skip0 : 0)) * N + key % N + 1;
           K = required;  // pairs the device had to evaluate (speculative tiles past the winner not counted)
           perf.scanPairs += K;
           perf.scanBytes += K * kBytesPerCandidate;
@@ -1616,6 +1677,7 @@ int64_t Device::scanQueue(const DevProgram& prog, int head, int skip0, const int
   // no server (or too many keys): the rows flattened for a plain cross scan, its key mapped back
   segFlat_.clear();
   std::vector<int32_t> entryOf, rowOf;
+  if (mir) return scanQueueKeyedFlat(prog, *mir, head, skip0 != 0, skipKey, tail, nTail, cands, N);
   for (int i = 0; i < n; ++i) {
     const auto& v = *qdirSnap_[entry(i)];
     for (size_t r = i == 0 ? (size_t)skip0 : 0; r < v.size(); ++r) {

@@ -17,6 +17,7 @@
 
 #include "devtypes.h"
 #include "intra.h"
+#include "keyed_table.h"
 #include "shard_group.h"
 #include "snapseg.h"
 
@@ -206,6 +207,54 @@ class Device {
   int64_t scanQueue(const DevProgram& prog, int head, int skip0, const int32_t* tail, int nTail, const int32_t* cands,
                     int N);
   int queueSpan() const { return qdirSpan_; }
+  // The keyed membership table (devtypes.h KeyedRow; the engine's KeyedMirror is its host mirror): the queue scans'
+  // rows without a sorted snapshot. kqBind: a table of B blocks of `stride` slots for `key`, every length 0 (false:
+  // too large to allocate). kqWriteRow / kqSetLen: one row / one length word through the BAR; the command that reads
+  // them is published behind a store fence.
+  // The table's entry points are installed by the Device that has one (device.cpp, at construction). A Device build
+  // without them has no table (hasKeyedTable() false): the engine then keeps only the mirror, and a keyed queue scan
+  // is scanQueueKeyedFlat.
+  struct KeyedOps {
+    bool (*bind)(Device&, uint64_t key, int stride) = nullptr;
+    void (*writeRow)(Device&, int b, int slot, int r, uint64_t key) = nullptr;
+    void (*setLen)(Device&, int b, int len) = nullptr;
+    int64_t (*scan)(Device&, const DevProgram& prog, const KeyedMirror& mir, int head, bool hasSkip, uint64_t skipKey,
+                    const int32_t* tail, int nTail, const int32_t* cands, int N) = nullptr;
+  };
+  bool hasKeyedTable() const { return keyedOps_.bind != nullptr; }
+  bool kqBind(uint64_t key, int stride) { return keyedOps_.bind(*this, key, stride); }
+  void kqUnbind() { kqKey_ = 0; }
+  uint64_t kqKey() const { return kqKey_; }
+  void kqWriteRow(int b, int slot, int r, uint64_t key) { keyedOps_.writeRow(*this, b, slot, r, key); }
+  void kqSetLen(int b, int len) { keyedOps_.setLen(*this, b, len); }
+  // scanQueue over the keyed table: an entry's rows in key order (entry 0: only keys above skipKey when hasSkip), so
+  // the key's row is the winner's slot and span = the table's stride. `mir` is the table's host mirror (accounting,
+  // and the rows of the flattened fallback).
+  int64_t scanQueueKeyed(const DevProgram& prog, const KeyedMirror& mir, int head, bool hasSkip, uint64_t skipKey,
+                         const int32_t* tail, int nTail, const int32_t* cands, int N) {
+    return keyedOps_.scan(*this, prog, mir, head, hasSkip, skipKey, tail, nTail, cands, N);
+  }
+  // The same scan without a device table: the mirror's blocks sorted by key and flattened into one cross scan
+  // (scanCross), its key mapped back to (entry, slot, column). Also what scanQueueKeyed falls back to without a server.
+  int64_t scanQueueKeyedFlat(const DevProgram& prog, const KeyedMirror& mir, int head, bool hasSkip, uint64_t skipKey,
+                             const int32_t* tail, int nTail, const int32_t* cands, int N) {
+    const int hasHead = head >= 0 ? 1 : 0, n = hasHead + nTail, span = mir.stride();
+    std::vector<int32_t> flat, entryOf, slotOf, v;
+    for (int i = 0; i < n; ++i) {
+      const int b = i < hasHead ? head : tail[i - hasHead];
+      mir.sorted(b, v);
+      for (size_t r = i == 0 && hasSkip ? (size_t)mir.below(b, skipKey + 1) : 0; r < v.size(); ++r) {
+        flat.push_back(v[r]);
+        entryOf.push_back(i);
+        slotOf.push_back(mir.slotOf(v[r]));
+      }
+    }
+    if (flat.empty() || N <= 0) return -1;
+    const int64_t k = scanCross(prog, flat.data(), (int)flat.size(), cands, N, 0, N);
+    if (k < 0) return -1;
+    const int64_t fr = k / N;
+    return ((int64_t)entryOf[fr] * span + slotOf[fr]) * N + k % N;
+  }
   // Shard groups (shard_group.h): the block every rank of the group maps, and the group's rank count. A served cross /
   // segment / pair scan is then combined by the server (takeDeviceCombined() reports it once); any other combine goes
   // through groupCombineHost on the same slot sequence.
@@ -575,6 +624,20 @@ class Device {
   int qdirSpan_ = 1;  // >= every set entry's length since the last bind
   QueueDirEntry* qdir_ = nullptr;  // fine-grained VRAM [B] (host-written through the BAR)
   std::vector<std::shared_ptr<const std::vector<int32_t>>> qdirSnap_;  // [B] the snapshot each entry points at
+  // keyed membership table: one fine-grained VRAM block, the length words [B] then the rows [B * kqStride_]
+  uint64_t kqKey_ = 0;
+  int kqStride_ = 0;
+  size_t kqBytes_ = 0;
+  char* kqMem_ = nullptr;
+  int32_t* kqLens_ = nullptr;
+  KeyedRow* kqRows_ = nullptr;
+  KeyedOps keyedOps_;
+  bool kqBindImpl(uint64_t key, int stride);
+  void kqWriteRowImpl(int b, int slot, int r, uint64_t key);
+  void kqSetLenImpl(int b, int len);
+  // scanQueue (mir null; skip0 rows of entry 0 skipped) and scanQueueKeyed (skip0 != 0: skipKey applies) in one
+  int64_t scanQueueImpl(const DevProgram& prog, const KeyedMirror* mir, int head, int skip0, uint64_t skipKey,
+                        const int32_t* tail, int nTail, const int32_t* cands, int N);
   void ensureFg(size_t bytes);
   int32_t* rowVisited_ = nullptr;
   size_t rowVisitedCap_ = 0;

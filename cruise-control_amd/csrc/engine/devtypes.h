@@ -420,6 +420,18 @@ struct QueueDirEntry {
   uint32_t off;  // pool index of the broker's first snapshot row
   int32_t len;   // its snapshot length
 };
+// SOP_QUEUE over the keyed membership table (ServerCmd.queueStride > 0; engine/keyed_table.h): entry i's rows are the
+// first lens[b] of broker b's block of `queueStride` slots, UNSORTED, each with its Model::replicaKey under the bound
+// Spec. The scan's row order is the key order, so an entry's winner is its accepted (row key, column) minimum, found
+// by evaluating every row of the entry; entry 0 takes only rows whose key is above ServerCmd.skipKey. The published key
+// keeps its form with row = the slot in the block and span = the stride. The host rewrites rows and lengths in place
+// between commands, so the device reads them with system-scope loads.
+struct alignas(8) KeyedRow {
+  uint64_t key;            // Model::replicaKey under the table's Spec
+  int32_t r, p, topic;     // RowRef minus the source broker (the entry's broker)
+  int32_t pad;
+};
+static_assert(sizeof(KeyedRow) == 24, "KeyedRow is three 8-byte words");
 // SOP_SEGS: a cross scan whose rows are the concatenation of nSegs segments of the device-resident snapshot pool
 // (Device::scanSegs); the segment table at oA holds {first pool entry, first row} per segment plus {0, K} at the end.
 constexpr int kMaxSegs = 1024;
@@ -460,6 +472,12 @@ struct alignas(16) ServerCmd {
   // SOP_PAIRS within one tile: this many workgroups (each goalParts waves) share the tile's goals — workgroup w takes
   // parts w * goalParts + wave % goalParts of wgParts * goalParts — and AND their accept masks (1: one workgroup)
   int32_t wgParts;
+  // SOP_QUEUE over the keyed membership table: slots per broker (0: the snapshot directory), the table's rows
+  // (KeyedRow[B * queueStride]; queueDir is then its length words, int32[B]) and the head entry's continuation (c0 != 0:
+  // entry 0 scans only rows with a key above skipKey)
+  int32_t queueStride;
+  unsigned long long queueRows;
+  unsigned long long skipKey;
 };
 // The sequence word: the host stores (next | kSeqBusy) before it rewrites the other fields and `next` after them, each
 // behind a store fence; a workgroup copies the header once it reads a new sequence that is not busy (the fields landed

@@ -13,6 +13,7 @@
 #include <thread>
 
 #include "device.h"
+#include "hostpool.h"
 #include "predicates.h"
 #include "rackrows.h"
 #include "prof.h"
@@ -454,17 +455,100 @@ bool Engine::queueReady(const GoalImpl& self, int action, const Model::Spec& spe
   return queueSyncTry(spec);
 }
 
-void Engine::queueSync(const Model::Spec& spec) {
-  if (!queueSyncTry(spec))
+void Engine::queueSync(const Model::Spec& spec, bool keyedOk) {
+  if (!queueSyncTry(spec, keyedOk))
     throw Unsupported("the snapshot directory outgrew the snapshot pool (CCMI_SNAPSHOT_POOL_ROWS) during a move-in loop");
+}
+
+// The keyed membership table current for `spec`: rebuilt whole (on the host pool) when it holds another Spec's rows,
+// otherwise one row write per logged (broker, replica) change since the last sync — the replica's row inserted or its
+// key rewritten while it is on that broker and selected, else removed. No snapshot is sorted. False when this Spec
+// keeps the snapshot directory: the knob, a sharded session, or a broker that outgrew its block (then until another
+// Spec is bound: a loop does not switch back).
+bool Engine::keyedSyncTry(const Model::Spec& spec, uint64_t key) {
+  const char* knob = std::getenv("CCMI_QUEUE_KEYED");  // (read per sync: two getenv calls against a device command)
+  if ((knob && knob[0] == '0') || shard.count > 1 || shard.fn) return false;
+  KeyedSync& k = ksync_;
+  if (k.refused == key) return false;
+  // a Device without the table (no entry points installed): the mirror alone, scanned flattened (Device::scanQueueKeyedFlat)
+  const bool table = dev->hasKeyedTable();
+  auto refuse = [&]() {
+    k.refused = key;
+    k.key = 0;
+    dev->kqUnbind();
+    prof().count(75, "queue.keyed.overflow", 1);
+    return false;
+  };
+  const auto t0 = prof().on ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
+  auto ns = [&] {
+    return (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+  };
+  if (k.key != key || (table && dev->kqKey() != key) || k.owner != (const void*)dev) {
+    // stride: the session's largest broker with a quarter of headroom (CCMI_QUEUE_KEYED_STRIDE: tests)
+    int largest = 0;
+    for (int b = 0; b < m.B; ++b) largest = std::max(largest, (int)m.bRepl[b].size());
+    int stride = (largest + largest / 4 + 16 + 7) & ~7;
+    if (const char* e = std::getenv("CCMI_QUEUE_KEYED_STRIDE")) stride = std::max(1, std::atoi(e));
+    k.key = 0;
+    if (table && !dev->kqBind(key, stride)) return refuse();
+    k.mir.reset(m.B, m.R, stride);
+    k.owner = dev;
+    std::atomic<bool> overflow{false};
+    constexpr int kChunk = 64;  // brokers per task: a block's rows and mirror entries belong to one task
+    HostPool::get().parallelFor((m.B + kChunk - 1) / kChunk, [&](int c) {
+      for (int b = c * kChunk, e = std::min(m.B, b + kChunk); b < e; ++b) {
+        for (int r : m.bRepl[b]) {
+          if (!m.selects(spec, r)) continue;
+          KeyedMirror::Write w;
+          bool lenChanged;
+          if (!k.mir.upsert(b, r, m.replicaKey(spec, r), &w, &lenChanged)) {
+            overflow.store(true);
+            break;
+          }
+          if (table) dev->kqWriteRow(b, w.slot, w.rep, w.key);
+        }
+        if (table) dev->kqSetLen(b, k.mir.len(b));
+      }
+    });
+    if (overflow.load()) return refuse();
+    k.key = key;
+    k.refused = 0;
+    k.logPos = m.verLog.size();
+    prof().count(20, "queue.dir.full", 1);
+    if (prof().on) prof().count(28, "queue.full.ns", ns());
+    return true;
+  }
+  const size_t end = m.verLog.size();
+  for (size_t q = k.logPos; q < end; ++q) {
+    const int b = m.verLog[q], r = m.verLogRep[q];
+    if (r < 0) continue;
+    KeyedMirror::Write w;
+    if (m.rBroker[r] == b && m.selects(spec, r)) {
+      bool lenChanged;
+      if (!k.mir.upsert(b, r, m.replicaKey(spec, r), &w, &lenChanged)) return refuse();
+      if (table) dev->kqWriteRow(b, w.slot, w.rep, w.key);
+      if (table && lenChanged) dev->kqSetLen(b, k.mir.len(b));
+    } else {
+      bool moved;
+      if (!k.mir.remove(b, r, &w, &moved)) continue;
+      if (table && moved) dev->kqWriteRow(b, w.slot, w.rep, w.key);
+      if (table) dev->kqSetLen(b, k.mir.len(b));
+    }
+  }
+  prof().count(76, "queue.keyed.changes", (int64_t)(end - k.logPos));
+  k.logPos = end;
+  if (prof().on) prof().count(30, "queue.inc.ns", ns());
+  return true;
 }
 
 // Every broker's directory entry current for `spec`: all of them when the directory was filled for another Spec (or
 // the pool wrapped under it), otherwise only the brokers relocations touched since the last sync (Model::verLog).
 // False when the directory's snapshots do not fit the pool together; the directory is then left unbound.
-bool Engine::queueSyncTry(const Model::Spec& spec) {
+bool Engine::queueSyncTry(const Model::Spec& spec, bool keyedOk) {
   PhaseScope ps(PH_FLATTEN);
   const uint64_t key = specKey(spec, m.selEpoch);
+  keyedCurrent_ = keyedOk && keyedSyncTry(spec, key);
+  if (keyedCurrent_) return true;
   QueueSync& q = qsync_;
   if (q.stamp.size() != (size_t)m.B) q.stamp.assign(m.B, 0);
   bool full = !q.bound || q.key != key || dev->qdirKey() != key || q.epoch != dev->poolEpoch();
@@ -519,28 +603,60 @@ bool Engine::queueSyncTry(const Model::Spec& spec) {
   return unbind();  // the pool keeps wrapping: the directory does not fit it
 }
 
-int64_t Engine::queueScan(GoalImpl& self, int action, const Model::Spec& spec, int head, int skip0,
-                          const int32_t* tail, int nTail, const std::vector<int32_t>& cands) {
+Engine::QueueHit Engine::queueScan(GoalImpl& self, int action, const Model::Spec& spec, int head, int skipIdx,
+                                   uint64_t skipKey, const int32_t* tail, int nTail,
+                                   const std::vector<int32_t>& cands) {
   const int hasHead = head >= 0 ? 1 : 0;
   const int n = hasHead + nTail, N = (int)cands.size();
-  if (n == 0 || N == 0) return -1;
+  QueueHit hit;
+  if (n == 0 || N == 0) return hit;
   PhaseScope ps(PH_DEV_SCAN);
+  const int skip0 = hasHead ? skipIdx : 0;
   queueSync(spec);
+  const bool keyed = keyedCurrent_;
+  const KeyedMirror& mir = ksync_.mir;
   m.flushToDevice();
   const DevProgram prog = program(self, action);
-  const int64_t key = dev->scanQueue(prog, head, skip0, tail, nTail, cands.data(), N);
+  auto entry = [&](int i) { return i < hasHead ? head : tail[i - hasHead]; };
+  int64_t key;
+  if (keyed) {
+    prof().count(74, "queue.keyed.scans", 1);
+    key = dev->hasKeyedTable()
+              ? dev->scanQueueKeyed(prog, mir, head, skip0 > 0, skipKey, tail, nTail, cands.data(), N)
+              : dev->scanQueueKeyedFlat(prog, mir, head, skip0 > 0, skipKey, tail, nTail, cands.data(), N);
+  } else {
+    key = dev->scanQueue(prog, head, skip0, tail, nTail, cands.data(), N);
+  }
   checkTerminal(key);
   // reference-equivalent candidates: every row of the entries before the winner's, then its rows up to the winner
-  const int span = dev->queueSpan();
+  const int span = keyed ? mir.stride() : dev->queueSpan();
   const int wi = key < 0 ? n : (int)(key / N / span);
   int64_t rows = 0;
   for (int i = 0; i < wi; ++i) {
-    const int len = dev->qdirLen(i < hasHead ? head : tail[i - hasHead]), s0 = i == 0 ? skip0 : 0;
+    const int len = keyed ? mir.len(entry(i)) : dev->qdirLen(entry(i)), s0 = i == 0 ? skip0 : 0;
     rows += len > s0 ? len - s0 : 0;
   }
-  if (key < 0) candidates += rows * N;
-  else candidates += (rows + (key / N) % span - (wi == 0 ? skip0 : 0)) * N + key % N + 1;
-  return key;
+  if (key < 0) {
+    candidates += rows * N;
+    return hit;
+  }
+  hit.key = key;
+  hit.entry = wi;
+  hit.cb = entry(wi);
+  const int row = (int)((key / N) % span);
+  if (keyed) {  // the row is the winner's slot: its view index is the number of the block's rows with a smaller key
+    hit.r = mir.rep(hit.cb, row);
+    hit.rowKey = mir.key(hit.cb, row);
+    hit.idx = mir.below(hit.cb, hit.rowKey);
+    hit.len = mir.len(hit.cb);
+  } else {
+    hit.r = dev->qdirRows(hit.cb)[row];  // cb's live view == the snapshot the scan read
+    hit.rowKey = m.replicaKey(spec, hit.r);
+    hit.idx = row;
+    hit.len = dev->qdirLen(hit.cb);
+  }
+  candidates += (rows + hit.idx - (wi == 0 ? skip0 : 0)) * N + key % N + 1;
+  return hit;
 }
 
 // CCMI_FORCE_COMBINE=1 sends single-shard keys through the combiner too (diagnostics: exercises the RCCL path of a
@@ -2170,7 +2286,7 @@ class ResourceDistribution : public GoalImpl {
     Model& m = e.m;
     std::vector<int32_t> merged;
     int curCb = -1, curSkip = 0;
-    const int N = (int)cands.size();
+    uint64_t curSkipKey = 0;
     while (curCb >= 0 || !pq.empty()) {
       // the queue's poll order: its remaining sorted run as it is, or (after a re-add) every element polled in order
       const bool run = pq.runOnly();
@@ -2182,13 +2298,10 @@ class ResourceDistribution : public GoalImpl {
       const int32_t* tail = run ? pq.runData() : merged.data();
       const int nTail = (int)(run ? pq.runLeft() : merged.size());
       const int head = curCb, hasHead = head >= 0 ? 1 : 0;
-      const int64_t key = e.queueScan(*this, DA_MOVE, spec, head, hasHead ? curSkip : 0, tail, nTail, cands);
-      if (key < 0) return true;  // every queued broker polled, nothing accepted
-      const int span = e.dev->queueSpan();
-      const int64_t row = key / N;
-      const int i = (int)(row / span), idx = (int)(row % span);
-      const int cb = i < hasHead ? head : tail[i - hasHead];
-      const int r = e.dev->qdirRows(cb)[idx];  // cb's live view == the snapshot the scan read
+      const Engine::QueueHit hit =
+          e.queueScan(*this, DA_MOVE, spec, head, hasHead ? curSkip : 0, curSkipKey, tail, nTail, cands);
+      if (hit.key < 0) return true;  // every queued broker polled, nothing accepted
+      const int i = hit.entry, idx = hit.idx, cb = hit.cb, r = hit.r;
       // the brokers up to the winner's are polled (the reference polled them); the ones after it stay queued
       const int polled = i < hasHead ? 0 : i - hasHead + 1;
       if (run) pq.skipRun((size_t)polled);
@@ -2206,7 +2319,8 @@ class ResourceDistribution : public GoalImpl {
       } else {
         prof().count(2, "in.move.continue");
         curCb = cb;
-        curSkip = idx;  // the reference's iteration resumes at the same index of the view without r
+        curSkip = idx;  // the reference's iteration resumes at the same index of the view without r:
+        curSkipKey = hit.rowKey;  // the rows whose key is above r's (taken before the relocation)
       }
     }
     return true;

@@ -22,6 +22,7 @@
 #include "ccmi.h"
 #include "devtypes.h"
 #include "errors.h"
+#include "keyed_table.h"
 #include "model.h"
 
 namespace ccmi {
@@ -180,9 +181,10 @@ class Engine {
   int64_t crossScanSegs(GoalImpl& self, int site, int action, const std::vector<SnapSeg>& segs,
                         const std::vector<int32_t>& cands);
   // Queue scans (Device::scanQueue): the rows of every broker of [head (if >= 0)] ++ tail[0, nTail) (poll order; entry 0
-  // from row skip0) x cands in
-  // ONE device command, each broker's rows its snapshot under `spec` from the device-resident snapshot directory.
-  // Returns the key (Device::scanQueue) or -1 and adds the reference-equivalent candidates. queueOn: the path applies
+  // from row skipIdx of its view) x cands in
+  // ONE device command, each broker's rows its view under `spec`: the keyed membership table's block, or its snapshot
+  // from the device-resident snapshot directory.
+  // Returns the winner (QueueHit) and adds the reference-equivalent candidates. queueOn: the path applies
   // (one shard, a usable server, no replica-dependent candidate filters; CCMI_QUEUE_SCAN=0 turns it off).
   bool queueOn(const GoalImpl& self, int action) const;
   // queueOn, and the snapshot directory set for `spec`: false when the directory does not fit the snapshot pool (the
@@ -192,9 +194,20 @@ class Engine {
   // Shard groups: the queue path is allowed only when every rank can take it (set at attach, ccmi_api.cpp)
   bool shardQueueAllowed = true;
   // the snapshot directory current for `spec` (Device::qdirRows / qdirLen then give every broker's live view)
-  void queueSyncSpec(const Model::Spec& spec) { queueSync(spec); }
-  int64_t queueScan(GoalImpl& self, int action, const Model::Spec& spec, int head, int skip0, const int32_t* tail,
-                    int nTail, const std::vector<int32_t>& cands);
+  void queueSyncSpec(const Model::Spec& spec) { queueSync(spec, false); }
+  // A queue scan's winner: its queue entry and broker, the replica, the replica's index in the broker's sorted view as
+  // the scan saw it (idx of len rows) and its sort key. A move-in loop that goes on with the same broker hands idx and
+  // rowKey back as the next scan's continuation: the view without the moved replica from the same index, which is the
+  // rows with a larger key.
+  struct QueueHit {
+    int64_t key = -1;  // Device::scanQueue's key, -1: nothing accepted
+    int entry = -1, cb = -1, r = -1, idx = 0, len = 0;
+    uint64_t rowKey = 0;
+  };
+  // The rows come from the keyed membership table (Device::scanQueueKeyed, CCMI_QUEUE_KEYED=0 turns it off) or from
+  // the snapshot directory; the result is the same either way.
+  QueueHit queueScan(GoalImpl& self, int action, const Model::Spec& spec, int head, int skipIdx, uint64_t skipKey,
+                     const int32_t* tail, int nTail, const std::vector<int32_t>& cands);
   int64_t exclLeadCount(const DevProgram& prog, const int32_t* reps, int K, const std::vector<int32_t>& cands,
                         int64_t key) const;
   bool blocked(const DevProgram& prog, int r, int b) const;
@@ -261,8 +274,22 @@ class Engine {
     std::vector<int32_t> todo;                                       // a sync's brokers (scratch)
   };
   QueueSync qsync_;
-  void queueSync(const Model::Spec& spec);
-  bool queueSyncTry(const Model::Spec& spec);  // queueSync, false (directory unbound) when it does not fit the pool
+  // The keyed membership table's catch-up state (keyed_table.h): the mirror, the Spec + selection it holds, the
+  // Model::verLog position it is current to, and the Spec whose rows outgrew the stride (it keeps the snapshot
+  // directory until another Spec is bound).
+  struct KeyedSync {
+    KeyedMirror mir;
+    uint64_t key = 0;  // 0: unbound
+    size_t logPos = 0;
+    uint64_t refused = 0;
+    const void* owner = nullptr;  // the device the table lives on
+  };
+  KeyedSync ksync_;
+  bool keyedSyncTry(const Model::Spec& spec, uint64_t key);  // false: this Spec takes the snapshot directory
+  bool keyedCurrent_ = false;  // the last queueSyncTry left the keyed table current (not the snapshot directory)
+  void queueSync(const Model::Spec& spec, bool keyedOk = true);
+  // queueSync, false (directory unbound) when it does not fit the pool
+  bool queueSyncTry(const Model::Spec& spec, bool keyedOk = true);
   DevProgram program(const GoalImpl& self, int action) const;
   int64_t combine(int64_t localKey) const;
   void refreshAllowed(GoalImpl& g);

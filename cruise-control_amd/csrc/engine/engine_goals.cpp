@@ -2137,7 +2137,7 @@ bool LeaderReplicaDistribution_moveInQueue(Engine& e, GoalImpl& self, int b, Q& 
   Model& m = e.m;
   std::vector<int32_t> merged;
   int curCb = -1, curSkip = 0;
-  const int N = (int)cands.size();
+  uint64_t curSkipKey = 0;
   while (curCb >= 0 || !pq.empty()) {
     const bool run = pq.heapEmpty();
     if (!run) {
@@ -2147,14 +2147,10 @@ bool LeaderReplicaDistribution_moveInQueue(Engine& e, GoalImpl& self, int b, Q& 
     const int32_t* tail = run ? pq.runData() : merged.data();
     const int nTail = (int)(run ? pq.runLeft() : merged.size());
     const int head = curCb, hasHead = head >= 0 ? 1 : 0;
-    const int64_t key = e.queueScan(self, DA_MOVE, spec, head, hasHead ? curSkip : 0, tail, nTail, cands);
-    if (key < 0) return true;  // every queued source exhausted; none is re-enqueued
-    const int span = e.dev->queueSpan();
-    const int64_t row = key / N;
-    const int i = (int)(row / span), idx = (int)(row % span);
-    const int cb = i < hasHead ? head : tail[i - hasHead];
-    const int r = e.dev->qdirRows(cb)[idx];
-    const int hitSize = e.dev->qdirLen(cb);
+    const Engine::QueueHit hit =
+        e.queueScan(self, DA_MOVE, spec, head, hasHead ? curSkip : 0, curSkipKey, tail, nTail, cands);
+    if (hit.key < 0) return true;  // every queued source exhausted; none is re-enqueued
+    const int i = hit.entry, idx = hit.idx, cb = hit.cb, r = hit.r, hitSize = hit.len;
     const int polled = i < hasHead ? 0 : i - hasHead + 1;
     if (run) pq.skipRun((size_t)polled);
     else
@@ -2167,6 +2163,7 @@ bool LeaderReplicaDistribution_moveInQueue(Engine& e, GoalImpl& self, int b, Q& 
     } else if (idx + 1 < hitSize) {
       curCb = cb;  // the view without the moved replica, from the same index
       curSkip = idx;
+      curSkipKey = hit.rowKey;
     } else {
       curCb = -1;
     }

@@ -582,6 +582,8 @@ void Model::relocateReplica(int p, int src, int dst) {
   verLog.push_back(src);
   verLog.push_back(dst);
   const int r = brokerRemove(src, p);
+  verLogRep.push_back(r);  // (kept in step with verLog even when the next line throws)
+  verLogRep.push_back(r);
   if (r < 0) throw std::runtime_error("Replica is not in the cluster.");
   noteDelta(src, r);
   noteDelta(dst, r);
@@ -680,6 +682,8 @@ bool Model::relocateLeadership(int p, int src, int dst) {
   bVer[dst]++;
   verLog.push_back(src);
   verLog.push_back(dst);
+  verLogRep.push_back(sr);
+  verLogRep.push_back(dr);
   noteDelta(src, sr);
   noteDelta(dst, dr);
   // Broker.makeFollower(src)

@@ -325,6 +325,9 @@ class Model {
   // Every version bump in order (src and dst of each relocation): readers that keep per-broker state derived from
   // snapshots (the queue scans' snapshot directory) catch up from their position instead of re-checking every broker.
   std::vector<int32_t> verLog;
+  // verLogRep[k]: the replica whose membership or sort key on verLog[k] changed at that bump (-1: none), for readers
+  // that keep per-replica state (the queue scans' keyed membership table)
+  std::vector<int32_t> verLogRep;
   // CCMI_PROFILE: when the last relocation happened (steady_clock nanoseconds; 0 before the first)
   int64_t lastRelocNs = 0;
   // bumped whenever the selection sets the Specs do not carry change (excluded / must topics)

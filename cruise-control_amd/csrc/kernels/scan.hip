@@ -748,6 +748,19 @@ __device__ __forceinline__ unsigned long long tileMask(bool ok, int parts) {
   return pass;
 }
 
+// Whether this lane's slot of a scan-server tile was accepted by every wave of its group (tileFirst's verdict per slot).
+__device__ __forceinline__ bool tilePass(bool ok, int parts) {
+  __shared__ unsigned long long sBalP[kBlock / 64];
+  const unsigned long long bal = __ballot(ok);
+  if ((threadIdx.x & 63) == 0) sBalP[threadIdx.x >> 6] = bal;
+  __syncthreads();
+  const int g = (int)(threadIdx.x >> 6) / parts;
+  unsigned long long pass = ~0ull;
+  for (int p = 0; p < parts; ++p) pass &= sBalP[g * parts + p];
+  __syncthreads();
+  return (pass >> (threadIdx.x & 63)) & 1ull;
+}
+
 // Last-arriver publish: every workgroup arrives once (after its final atomicMin); the last one reads the
 // winning key and writes ONE 64-bit word {seq:32 | key+1:32} (0 in the low half = no winner) to the host
 // mailbox — a single aligned 8-byte store, so the host never sees a sequence number without its key and
@@ -1364,7 +1377,21 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, kServ
       // their rows as ONE range — its brokers' (row, column) pairs back to back, a prefix sum in LDS — in tiles of
       // kBlock / parts slots, so a tile spans several short snapshots. Keys grow with (entry, row, column) along that
       // range, so the early exits keep the first fit exact.
+      // Over the keyed membership table (c.queueStride > 0) an entry's rows are its block's first `len` slots in NO
+      // order, each with its sort key: the workgroup evaluates every row of an entry and keeps the accepted (row key,
+      // column) minimum in LDS, and publishes that one key only after the entry's last row — exactly one workgroup owns
+      // an entry, so it publishes at most one key per entry and the result word works as before. It stops at its
+      // first entry with an accept, or when the current best belongs to a smaller entry. The host rewrites rows and
+      // lengths in place between commands: they are read with system-scope loads, like the command's payload.
       const int n = c.n, N = c.N, span = c.K, skip0 = c.c0;
+      const int stride = c.queueStride;
+      const bool keyed = stride > 0;
+      const unsigned long long skipKey = c.skipKey;
+      const int32_t* kqLens = reinterpret_cast<const int32_t*>(c.queueDir);
+      const KeyedRow* kqRows = reinterpret_cast<const KeyedRow*>(c.queueRows);
+      __shared__ unsigned long long sMinKey, sMinPub;  // keyed: the pending entry's least accepted row key, its best key
+      __shared__ int sPend;
+      int pend = -1;  // keyed: the batch entry with an accept whose rows are not all evaluated yet (block-uniform)
       const int parts = (c.goalParts == 2 || c.goalParts == 4) ? c.goalParts : 1;
       const uint32_t tile = (uint32_t)(kBlock / parts);
       const int wave = (int)(threadIdx.x >> 6);
@@ -1386,11 +1413,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, kServ
         if ((int)threadIdx.x < nb) {
           const int i = wgI + (kb + (int)threadIdx.x) * (int)nAct;
           const int b = ldSys(Q + i);
-          const unsigned long long e = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(dir + b),
-                                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          const int len = (int)(uint32_t)(e >> 32), r0 = i == 0 ? skip0 : 0;
-          cnt = len > r0 ? (uint32_t)(len - r0) * (uint32_t)N : 0u;
-          sOff[threadIdx.x] = (uint32_t)(e & 0xffffffffull) + (uint32_t)r0;
+          if (keyed) {  // every slot of the block is walked (entry 0's rows at or below skipKey are masked, not cut)
+            const int len = min(max(ldSys(kqLens + b), 0), stride);
+            cnt = (uint32_t)len * (uint32_t)N;
+            sOff[threadIdx.x] = (uint32_t)b;
+          } else {
+            const unsigned long long e = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(dir + b),
+                                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            const int len = (int)(uint32_t)(e >> 32), r0 = i == 0 ? skip0 : 0;
+            cnt = len > r0 ? (uint32_t)(len - r0) * (uint32_t)N : 0u;
+            sOff[threadIdx.x] = (uint32_t)(e & 0xffffffffull) + (uint32_t)r0;
+          }
         }
         // exclusive prefix of cnt over the block (wave scans, then the wave totals)
         {
@@ -1415,12 +1448,21 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, kServ
         // this slot's pair of the NEXT tile, loaded while the current one is evaluated (software pipelining of the
         // fine-grained pool reads: a tile's critical path is then its record loads and the conjunction)
         RowRef nextRq{0, 0, 0, 0};
+        unsigned long long nextKey = 0;
         int nextK = 0;
         bool haveNext = false;
-        auto rowAt = [&](uint32_t v, int& k) {  // the pool row of pair v (k: its entry, advanced from the caller's)
+        // the row of pair v (k: its entry, advanced from the caller's; rk: a keyed row's sort key)
+        auto rowAt = [&](uint32_t v, int& k, unsigned long long& rk) {
           while (k + 1 < nb && sPre[k + 1] <= v) ++k;
+          if (keyed) {
+            const int b = (int)sOff[k];
+            const KeyedRow* row = kqRows + (size_t)b * (size_t)stride + (v - sPre[k]) / (uint32_t)N;
+            rk = __hip_atomic_load(&row->key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            return RowRef{ldSys(&row->r), b, ldSys(&row->p), ldSys(&row->topic)};
+          }
           return pool[sOff[k] + (v - sPre[k]) / (uint32_t)N];  // written before any command read it (a ring)
         };
+        pend = -1;
         for (uint32_t base = 0; base < total; base += tile) {
           // the tile's first pair: its key bounds every key of the tile from below
           int kf = 0;
@@ -1436,23 +1478,29 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, kServ
           auto keyOf = [&](int k, uint32_t v) {  // key of pair v of the range, inside batch entry k
             const int i = wgI + (kb + k) * (int)nAct;
             const uint32_t w = v - sPre[k];
-            const uint32_t row = (uint32_t)(i == 0 ? skip0 : 0) + w / (uint32_t)N;
+            const uint32_t row = (uint32_t)(i == 0 && !keyed ? skip0 : 0) + w / (uint32_t)N;
             return ((unsigned long long)i * (unsigned long long)span + row) * (unsigned long long)N + w % (uint32_t)N;
           };
-          if (!firstTile && blockBest(result) <= keyOf(kf, base)) {
+          // keyed: the pending entry's rows are all evaluated once a tile starts past it
+          if (pend >= 0 && kf > pend) break;
+          // keyed rows are in no order: only a best in a smaller ENTRY ends the walk (keyOf of the entry's first pair);
+          // no other workgroup publishes into this one's entries
+          if (!firstTile && pend < 0 && blockBest(result) <= keyOf(kf, keyed ? sPre[kf] : base)) {
             found = true;  // a smaller key exists: nothing later in this workgroup's range can win
             break;
           }
           const uint32_t v = base + slot;
           RowRef rq{0, 0, 0, 0};
+          unsigned long long rk = 0;
           int dq = 0;
           int k = kf;
           if (v < total) {
             if (haveNext) {
               rq = nextRq;
+              rk = nextKey;
               k = nextK;
             } else {
-              rq = rowAt(v, k);
+              rq = rowAt(v, k, rk);
             }
             const uint32_t w = v - sPre[k];
             dq = candsLds ? sCand[w % (uint32_t)N] : ldSys(C + w % (uint32_t)N);
@@ -1460,12 +1508,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, kServ
           haveNext = false;
           if (v + tile < total) {  // the next tile's row of this slot (a tile spans a few entries)
             nextK = k;
-            nextRq = rowAt(v + tile, nextK);
+            nextRq = rowAt(v + tile, nextK, nextKey);
             haveNext = true;
           }
           if (!staged) stage();
           bool ok = false;
-          if (v < total) {
+          // (the head entry's continuation: its rows at or below the moved replica's key were walked before)
+          const bool masked = keyed && skip0 && rk <= skipKey && wgI + (kb + k) * (int)nAct == 0;
+          if (v < total && !masked) {
             PreView pv;
             pv.loadDst(T, dq, ov);
             pv.loadRowRef(T, prog, rq, ov);
@@ -1480,11 +1530,41 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, kServ
           ++qTiles;
           if (T.stamps && threadIdx.x == 0)
             atomicAdd(&T.stamps[8220 + SOP_QUEUE], (unsigned long long)min(tile, total - base));
-          if (f >= 0) {
+          if (f >= 0 && keyed) {
+            // The tile holds an accept. Its slots' verdicts (every part's, ANDed) give, in LDS: the first entry with
+            // an accept (it becomes the pending entry), that entry's least accepted row key, and the least key among
+            // the accepted pairs of that row. Tiles without an accept pay nothing here.
+            const bool mineOk = tilePass(ok, parts) && part == 0;  // one lane per accepted slot
+            if (pend < 0) {
+              if (threadIdx.x == 0) {
+                sPend = 0x7fffffff;
+                sMinKey = ~0ull;
+                sMinPub = ~0ull;
+              }
+              __syncthreads();
+              if (mineOk) atomicMin(&sPend, k);
+              __syncthreads();
+              pend = sPend;
+            }
+            const bool inPend = mineOk && k == pend;
+            const unsigned long long before = sMinKey;
+            __syncthreads();
+            if (inPend) atomicMin(&sMinKey, rk);
+            __syncthreads();
+            const unsigned long long least = sMinKey;
+            if (least < before && threadIdx.x == 0) sMinPub = ~0ull;  // a smaller row: the earlier row's pairs lose
+            __syncthreads();
+            if (inPend && rk == least) atomicMin(&sMinPub, keyOf(k, v));
+            __syncthreads();
+          } else if (f >= 0) {
             if (threadIdx.x == (unsigned)(f % 64) + (unsigned)((f / 64) * parts * 64)) atomicMin(result, keyOf(k, v));
             found = true;
             break;
           }
+        }
+        if (pend >= 0) {  // keyed: the entry's last row is behind: its one key
+          if (threadIdx.x == 0 && sMinPub != ~0ull) atomicMin(result, sMinPub);
+          found = true;
         }
         __syncthreads();  // the batch arrays are rewritten by the next batch
       }
