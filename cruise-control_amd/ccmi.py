@@ -272,6 +272,22 @@ class PlanSummaryStruct(C.Structure):  # ccmi_plan_summary, 64 bytes
                 ("mingled", C.c_int64), ("reserved", C.c_int64)]
 
 
+class QueueProbeArgsStruct(C.Structure):  # ccmi_queue_probe_args (csrc/ccmi_session.h: diagnostics, not in the ABI)
+    _fields_ = [("sel_leaders", C.c_int32), ("score_res", C.c_int32), ("score_reverse", C.c_int32),
+                ("prio_offline", C.c_int32), ("prio_immigrants", C.c_int32), ("sel_excl_topics", C.c_int32),
+                ("self_kind", C.c_int32), ("num_accept", C.c_int32), ("accept_kinds", C.POINTER(C.c_int32)),
+                ("head", C.c_int32), ("has_skip", C.c_int32), ("skip_key", C.c_uint64),
+                ("tail", C.POINTER(C.c_int32)), ("n_tail", C.c_int32), ("cands", C.POINTER(C.c_int32)),
+                ("n_cands", C.c_int32), ("mode", C.c_int32)]
+
+
+class QueueProbeReportStruct(C.Structure):  # ccmi_queue_probe_report
+    _fields_ = [(f, C.c_int32) for f in (
+        "dev_entry", "dev_replica", "dev_column", "ref_entry", "ref_replica", "ref_column", "served", "keyed", "stride",
+        "n_active", "audit", "audited", "win_slot", "accepted_rows", "lowest_accepted_slot", "highest_accepted_slot",
+        "win_len", "win_rank", "head_masked", "pad")] + [("win_key", C.c_uint64)]
+
+
 class AggregatorConfigStruct(C.Structure):  # ccmi_aggregator_config, 32 bytes
     _fields_ = [("window_ms", C.c_int64), ("num_windows", C.c_int32), ("min_samples_per_window", C.c_int32),
                 ("num_metrics", C.c_int32), ("num_entities", C.c_int32), ("num_groups", C.c_int32),
@@ -473,6 +489,14 @@ class Library:
             L.ccmi_aggregator_remove_entities.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
             L.ccmi_aggregator_clear.argtypes = [C.c_void_p]
         L.ccmi_session_apply.argtypes = [C.c_void_p, C.POINTER(ActionStruct), C.c_int64, C.POINTER(C.c_int64)]
+        # diagnostics, outside the ABI (csrc/ccmi_session.h)
+        self.has_queue_probe = hasattr(L, "ccmi_queue_probe")
+        if self.has_queue_probe:
+            L.ccmi_queue_probe.argtypes = [C.c_void_p, C.POINTER(QueueProbeArgsStruct),
+                                           C.POINTER(QueueProbeReportStruct)]
+            L.ccmi_queue_probe_view.argtypes = [C.c_void_p, C.POINTER(QueueProbeArgsStruct), C.c_int32,
+                                                C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                C.c_int32, C.POINTER(C.c_int32)]
         # additive at ABI v13: the symbol's presence is the capability flag (also of goal kind 24)
         self.has_remove_disks = hasattr(L, "ccmi_session_mark_disks_for_removal")
         if self.has_remove_disks:
@@ -2212,6 +2236,57 @@ class ClusterModel:
         done = C.c_int64()
         self.lib.check(self.lib.lib.ccmi_session_apply(self.handle, arr, len(acts), C.byref(done)))
         return done.value
+
+    # ---- queue-scan diagnostics (ccmi_queue_probe, csrc/ccmi_session.h): not part of the ABI
+    @staticmethod
+    def _queue_probe_args(spec, self_goal="ReplicaDistributionGoal", accept_goals=(), head=-1, skip_key=None, tail=(),
+                          cands=(), mode=0):
+        """(QueueProbeArgsStruct, the arrays it points into). `spec`: a dict of the struct's Spec fields (leaders,
+        score_res, reverse, prio_offline, prio_immigrants, excl_topics); skip_key None: no continuation."""
+        a = QueueProbeArgsStruct()
+        a.sel_leaders = int(bool(spec.get("leaders", False)))
+        a.score_res = int(spec.get("score_res", -1))
+        a.score_reverse = int(bool(spec.get("reverse", False)))
+        a.prio_offline = int(bool(spec.get("prio_offline", False)))
+        a.prio_immigrants = int(bool(spec.get("prio_immigrants", False)))
+        a.sel_excl_topics = int(bool(spec.get("excl_topics", False)))
+        kinds = [goal_kind(g) for g in accept_goals]
+        keep = [(C.c_int32 * max(1, len(kinds)))(*kinds), (C.c_int32 * max(1, len(tail)))(*tail),
+                (C.c_int32 * max(1, len(cands)))(*cands)]
+        a.self_kind, a.num_accept, a.accept_kinds = goal_kind(self_goal), len(kinds), keep[0]
+        a.head, a.has_skip, a.skip_key = int(head), int(skip_key is not None), int(skip_key or 0)
+        a.tail, a.n_tail, a.cands, a.n_cands, a.mode = keep[1], len(tail), keep[2], len(cands), int(mode)
+        return a, keep
+
+    def _queue_probe(self, spec, self_goal="ReplicaDistributionGoal", accept_goals=(), head=-1, skip_key=None, tail=(),
+                     cands=(), mode=0) -> Dict[str, int]:
+        """One queue scan over the entries [head] ++ tail x cands with `self_goal` as the goal being optimized and
+        `accept_goals` as the optimized goals, next to a host loop's answer: the report's fields by name, with `dev` and
+        `ref` the (entry, replica, column) winners or None. mode 1 leaves out the table audit, mode 2 runs the host loop only."""
+        if not self.lib.has_queue_probe:
+            self._not_exported("ccmi_queue_probe", "a diagnostics build has it")
+        a, keep = self._queue_probe_args(spec, self_goal, accept_goals, head, skip_key, tail, cands, mode)
+        out = QueueProbeReportStruct()
+        self.lib.check(self.lib.lib.ccmi_queue_probe(self.handle, C.byref(a), C.byref(out)))
+        rep = {f: getattr(out, f) for f, _ in QueueProbeReportStruct._fields_}
+        rep["dev"] = None if out.dev_entry < 0 else (out.dev_entry, out.dev_replica, out.dev_column)
+        rep["ref"] = None if out.ref_entry < 0 else (out.ref_entry, out.ref_replica, out.ref_column)
+        return rep
+
+    def _queue_probe_view(self, spec, broker: int, slots: bool = False) -> List[tuple]:
+        """Broker `broker`'s rows under `spec` as the model has them: (key, replica) in key order; with `slots` also
+        each replica's slot in the keyed mirror's block as the last queue sync left it (-1: none)."""
+        if not self.lib.has_queue_probe:
+            self._not_exported("ccmi_queue_probe_view", "a diagnostics build has it")
+        a, keep = self._queue_probe_args(spec)
+        n = C.c_int32()
+        self.lib.check(self.lib.lib.ccmi_queue_probe_view(self.handle, C.byref(a), broker, None, None, None, 0,
+                                                          C.byref(n)))
+        k = max(1, n.value)
+        keys, reps, slot = (C.c_uint64 * k)(), (C.c_int32 * k)(), (C.c_int32 * k)()
+        self.lib.check(self.lib.lib.ccmi_queue_probe_view(self.handle, C.byref(a), broker, keys, reps, slot, n.value,
+                                                          C.byref(n)))
+        return [(keys[i], reps[i]) + ((slot[i],) if slots else ()) for i in range(n.value)]
 
     def _disks_of(self, broker_logdirs) -> List[int]:
         """Desc disk indices of {broker id: logdirs}; an unknown broker id or logdir is the reference's "Invalid log

@@ -1586,7 +1586,7 @@ int64_t Device::scanQueueImpl(const DevProgram& prog, const KeyedMirror* mir, in
   // the leading rows (in sort order) of entry i the scan passes over: the head entry's continuation
   auto skipped = [&](int i) {
     if (i != 0 || !skip0) return 0;
-    return mir ? mir->below(entry(0), skipKey + 1) : skip0;
+    return mir ? mir->atOrBelow(entry(0), skipKey) : skip0;
   };
   auto lenOf = [&](int i) { return mir ? mir->len(entry(i)) : qdirLen(entry(i)); };
   const uint64_t space = (uint64_t)n * (uint64_t)span * (uint64_t)N;
@@ -1623,6 +1623,7 @@ int64_t Device::scanQueueImpl(const DevProgram& prog, const KeyedMirror* mir, in
         // deepest of the last 8 winners, the extra sweeps cost 26 us per queue command on C2 against 0.25 GB less
         // traffic, profiles/r05/README.md)
         c.nActive = std::min(serverBlocks_, std::max(8, (n + 7) / 8 * 8));
+        queueLastActive = c.nActive;
         c.nb = g.nb;
         c.nr = g.nr;
         c.np = g.np;

@@ -10,6 +10,7 @@
 #pragma once
 #include <functional>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <unordered_map>
 #include <memory>
@@ -227,6 +228,14 @@ class Device {
   uint64_t kqKey() const { return kqKey_; }
   void kqWriteRow(int b, int slot, int r, uint64_t key) { keyedOps_.writeRow(*this, b, slot, r, key); }
   void kqSetLen(int b, int len) { keyedOps_.setLen(*this, b, len); }
+  // Diagnostics (ccmi_queue_probe.cpp): the table read back through the host mapping the rows were written through,
+  // and the workgroups the last served queue command was sent to (0: none was served yet)
+  int kqStride() const { return kqStride_; }
+  int32_t kqLenAt(int b) const { return *reinterpret_cast<const volatile int32_t*>(&kqLens_[b]); }
+  void kqReadBlock(int b, int len, KeyedRow* out) const {  // one copy per block: wide loads through the BAR
+    std::memcpy(out, &kqRows_[(size_t)b * (size_t)kqStride_], (size_t)len * sizeof(KeyedRow));
+  }
+  int queueLastActive = 0;
   // scanQueue over the keyed table: an entry's rows in key order (entry 0: only keys above skipKey when hasSkip), so
   // the key's row is the winner's slot and span = the table's stride. `mir` is the table's host mirror (accounting,
   // and the rows of the flattened fallback).
@@ -243,7 +252,7 @@ class Device {
     for (int i = 0; i < n; ++i) {
       const int b = i < hasHead ? head : tail[i - hasHead];
       mir.sorted(b, v);
-      for (size_t r = i == 0 && hasSkip ? (size_t)mir.below(b, skipKey + 1) : 0; r < v.size(); ++r) {
+      for (size_t r = i == 0 && hasSkip ? (size_t)mir.atOrBelow(b, skipKey) : 0; r < v.size(); ++r) {
         flat.push_back(v[r]);
         entryOf.push_back(i);
         slotOf.push_back(mir.slotOf(v[r]));

@@ -14,6 +14,7 @@
 
 #include "device.h"
 #include "hostpool.h"
+#include "host_view.h"
 #include "predicates.h"
 #include "rackrows.h"
 #include "prof.h"
@@ -44,67 +45,6 @@ const size_t kIdleSnapshots = envCount("CCMI_IDLE_SNAPSHOTS", 8);
 // puts of the speculative entry tree per poll of an in-flight move-out scan; 0 = off (read per call: tests vary it)
 size_t idleTreePuts() { return envCount("CCMI_IDLE_TREE_PUTS", 64); }
 constexpr size_t kMaxBatchRows = (size_t)1 << 18;
-
-// Host view of the model for predicates.h (same expressions the kernels evaluate).
-struct HostView {
-  const Model& m;
-  const std::vector<const std::vector<uint8_t>*>& allowedBySlot;
-  const std::vector<int32_t>& tUp;
-  const std::vector<int32_t>& tLo;
-  const std::vector<int32_t>& bSet;  // BrokerSetAwareGoal: broker set of every broker / replica (empty: none)
-  const std::vector<int32_t>& rSet;
-  const std::vector<int32_t>& tMin;  // MinTopicLeadersPerBrokerGoal minima (empty: none)
-  const std::vector<int32_t>& tLim;  // TopicLeaderReplicaDistributionGoal limits [T][2] (empty: none)
-  double bu(int b, int res) const { return m.bu(b, res); }
-  double bcap(int b, int res) const { return m.cap(b, res); }
-  bool hostMode() const { return m.hostMode(); }
-  double hu(int b, int res) const { return m.hu(b, res); }
-  double hcap(int b, int res) const { return m.hcap(b, res); }
-  int nrep(int b) const { return m.nrep(b); }
-  bool alive(int b) const { return m.alive(b); }
-  bool allowed(int slot, int b) const { return (*allowedBySlot[slot])[b] != 0; }
-  double ru(int r, int res) const { return m.ru(r, res); }
-  int flags(int r) const { return (m.rLeader[r] ? RF_LEADER : 0) | (m.rOrigOff[r] ? RF_ORIG_OFFLINE : 0); }
-  int rbroker(int r) const { return m.rBroker[r]; }
-  int rorig(int r) const { return m.rOrig[r]; }
-  bool origOff(int r) const { return m.origOffline(r); }
-  int rpart(int r) const { return m.rPart[r]; }
-  int pbegin(int p) const { return m.pOff[p]; }
-  int pend(int p) const { return m.pOff[p + 1]; }
-  int pbroker(int i) const { return m.rBroker[m.pSlots[i]]; }
-  bool hosts(int p, int b) const {
-    bool has = false;
-    for (int i = pbegin(p); i < pend(p); ++i) has |= (pbroker(i) == b);
-    return has;
-  }
-  int rack(int b) const { return m.bRack[b]; }
-  bool ineligible(int p, int b) const { return m.ineligible(p, b); }
-  bool otherOnRack(int p, int self, int rk) const {
-    for (int i = pbegin(p); i < pend(p); ++i)
-      if (pbroker(i) != self && m.bRack[pbroker(i)] == rk) return true;
-    return false;
-  }
-  int slotRack(int, int b) const { return m.bRack[b]; }
-  int rackCount(int p, int rk) const {
-    int c = 0;
-    for (int i = pbegin(p); i < pend(p); ++i) c += m.bRack[pbroker(i)] == rk ? 1 : 0;
-    return c;
-  }
-  int nlead(int b) const { return m.bNlead[b]; }
-  double pot(int b) const { return m.potNwOut(b); }
-  double lnwin(int b) const { return m.leadNwIn(b); }
-  double pLeadNwOut(int p) const { return m.pLeadNwOut(p); }
-  int ptopic(int p) const { return m.pTopic[p]; }
-  int tcount(int t, int b) const { return m.tcount(t, b); }
-  int tUpper(int t) const { return tUp[t]; }
-  int tLower(int t) const { return tLo[t]; }
-  int bset(int b) const { return bSet.empty() ? -1 : bSet[b]; }
-  int rbset(int r) const { return rSet.empty() ? -1 : rSet[r]; }
-  int tlead(int t, int b) const { return m.tlead(t, b); }
-  int tMinLead(int t) const { return tMin.empty() ? -1 : tMin[t]; }
-  int tLeadUpper(int t) const { return tLim[2 * t]; }
-  int tLeadLower(int t) const { return tLim[2 * t + 1]; }
-};
 
 uint32_t needsOf(const DevGoal& g) {
   switch (g.kind) {
@@ -154,16 +94,20 @@ double Engine::threshold(double avgPct, int res, bool lower) const {
 }
 
 DevProgram Engine::program(const GoalImpl& self, int action) const {
-  DevProgram p;
-  std::memset(&p, 0, sizeof(p));
-  p.action = action;
   // the conjunction of AnalyzerUtils.isProposalAcceptableForOptimizedGoals ends at a terminal goal (it throws)
   size_t nOpt = 0;
   while (nOpt < priors.size() && !(nOpt > 0 && priors[nOpt - 1]->terminal)) ++nOpt;
+  return programOf(self, priors.data(), nOpt, action);
+}
+
+DevProgram Engine::programOf(const GoalImpl& self, const GoalImpl* const* accept, size_t nOpt, int action) const {
+  DevProgram p;
+  std::memset(&p, 0, sizeof(p));
+  p.action = action;
   p.nGoals = 1 + (int)nOpt;
   if (p.nGoals > kMaxGoals) throw Unsupported("too many goals in one chain");
   p.goals[0] = self.dg;
-  for (size_t i = 0; i < nOpt; ++i) p.goals[i + 1] = priors[i]->dg;
+  for (size_t i = 0; i < nOpt; ++i) p.goals[i + 1] = accept[i]->dg;
   p.needs = 0;
   for (int i = 0; i < p.nGoals; ++i) p.needs |= needsOf(p.goals[i]);
   p.filter = FILTER_NONE;
@@ -606,6 +550,13 @@ bool Engine::queueSyncTry(const Model::Spec& spec, bool keyedOk) {
 Engine::QueueHit Engine::queueScan(GoalImpl& self, int action, const Model::Spec& spec, int head, int skipIdx,
                                    uint64_t skipKey, const int32_t* tail, int nTail,
                                    const std::vector<int32_t>& cands) {
+  if ((head >= 0 ? 1 : 0) + nTail == 0 || cands.empty()) return QueueHit();
+  return queueScanProg(program(self, action), spec, head, skipIdx, skipKey, tail, nTail, cands);
+}
+
+Engine::QueueHit Engine::queueScanProg(const DevProgram& prog, const Model::Spec& spec, int head, int skipIdx,
+                                       uint64_t skipKey, const int32_t* tail, int nTail,
+                                       const std::vector<int32_t>& cands) {
   const int hasHead = head >= 0 ? 1 : 0;
   const int n = hasHead + nTail, N = (int)cands.size();
   QueueHit hit;
@@ -616,7 +567,6 @@ Engine::QueueHit Engine::queueScan(GoalImpl& self, int action, const Model::Spec
   const bool keyed = keyedCurrent_;
   const KeyedMirror& mir = ksync_.mir;
   m.flushToDevice();
-  const DevProgram prog = program(self, action);
   auto entry = [&](int i) { return i < hasHead ? head : tail[i - hasHead]; };
   int64_t key;
   if (keyed) {

@@ -208,6 +208,15 @@ class Engine {
   // the snapshot directory; the result is the same either way.
   QueueHit queueScan(GoalImpl& self, int action, const Model::Spec& spec, int head, int skipIdx, uint64_t skipKey,
                      const int32_t* tail, int nTail, const std::vector<int32_t>& cands);
+  // queueScan's core over a given program (queueScan sends program(self, action))
+  QueueHit queueScanProg(const DevProgram& prog, const Model::Spec& spec, int head, int skipIdx, uint64_t skipKey,
+                         const int32_t* tail, int nTail, const std::vector<int32_t>& cands);
+  // Diagnostics (ccmi_queue_probe.cpp). programOf: the program of `self` as the goal being optimized with nAccept
+  // optimized goals as the acceptance conjunction (program(): the running optimization's priors). queueKeyedCurrent /
+  // queueMirror: what the last queue sync left.
+  DevProgram programOf(const GoalImpl& self, const GoalImpl* const* accept, size_t nAccept, int action) const;
+  bool queueKeyedCurrent() const { return keyedCurrent_; }
+  const KeyedMirror& queueMirror() const { return ksync_.mir; }
   int64_t exclLeadCount(const DevProgram& prog, const int32_t* reps, int K, const std::vector<int32_t>& cands,
                         int64_t key) const;
   bool blocked(const DevProgram& prog, int r, int b) const;

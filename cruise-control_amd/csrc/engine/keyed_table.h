@@ -81,6 +81,14 @@ class KeyedMirror {
     for (int s = 0, e = len_[(size_t)b]; s < e; ++s) n += key_[base + s] < k ? 1 : 0;
     return n;
   }
+  // rows of b whose key is `k` or below: what a continuation behind the row with key k passes over (not below(k + 1),
+  // which wraps at the largest key)
+  int atOrBelow(int b, uint64_t k) const {
+    const size_t base = (size_t)b * stride_;
+    int n = 0;
+    for (int s = 0, e = len_[(size_t)b]; s < e; ++s) n += key_[base + s] <= k ? 1 : 0;
+    return n;
+  }
   // b's replicas in key order (the sorted snapshot of the block), for the paths that need whole sorted rows
   void sorted(int b, std::vector<int32_t>& out) const;
 

@@ -56,8 +56,10 @@ static void compare(const KeyedMirror& m, const Shadow& sh, const std::vector<st
       CHECK(i < v.size() && v[i] == e.second, "step %d broker %d: sorted view at %zu", step, b, i);
       CHECK(m.below(b, e.first) == (int)i, "step %d broker %d: below(key of row %zu) = %d", step, b, i, m.below(b, e.first));
       CHECK(m.below(b, e.first + 1) == (int)i + 1, "step %d broker %d: below(key + 1) of row %zu", step, b, i);
+      CHECK(m.atOrBelow(b, e.first) == (int)i + 1, "step %d broker %d: atOrBelow(key of row %zu)", step, b, i);
       ++i;
     }
+    CHECK(m.atOrBelow(b, ~0ull) == (int)ref[b].size(), "step %d broker %d: atOrBelow(the largest key)", step, b);
     CHECK(v.size() == ref[b].size(), "step %d broker %d: sorted view size", step, b);
     CHECK(m.below(b, 0) == 0 && m.below(b, ~0ull) == (int)ref[b].size(), "step %d broker %d: below at the ends", step, b);
     const uint64_t probe = rng() >> 20;

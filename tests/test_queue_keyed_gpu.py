@@ -1,5 +1,6 @@
 """Queue scans over the keyed membership table on the device (scan_server's SOP_QUEUE over KeyedRow blocks): parity with
-the oracle with the table on and off, with the goal conjunction split over the waves (CCMI_GOAL_SPLIT=1) and with a small
+the oracle with the table on and off, with the run's other scans split over the waves (CCMI_GOAL_SPLIT=1; queue commands
+stay unsplit) and with a small
 snapshot pool (CCMI_SNAPSHOT_POOL_ROWS: the segment path still uses the pool). Child processes, as test_queue_keyed.py."""
 import pytest
 
@@ -22,6 +23,9 @@ def test_gpu_keyed_queue_matches_oracle(built, case, keyed):
 
 
 def test_gpu_keyed_queue_goal_split(built):
+    """The whole run with CCMI_GOAL_SPLIT=1: the split (several waves per candidate) applies to the run's cross, segment
+    and pair scans. Queue commands always carry goalParts = 1 (Device::scanQueueImpl), so the keyed queue scans
+    themselves run unsplit here; what this covers is that they stay correct next to split scans on the same server."""
     check_counters(run_worker("gpu", "b300_c1", CCMI_QUEUE_KEYED="1", CCMI_GOAL_SPLIT="1"), True)
 
 
