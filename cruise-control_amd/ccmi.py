@@ -319,6 +319,15 @@ class AggregatorCompletenessStruct(C.Structure):  # ccmi_aggregator_completeness
                 ("extrapolated_entity_ratio_by_window", C.POINTER(C.c_float))]
 
 
+class PartitionTopologyStruct(C.Structure):  # ccmi_partition_topology, 88 bytes
+    _fields_ = [("num_partitions", C.c_int32), ("num_topics", C.c_int32), ("num_logdirs", C.c_int32),
+                ("reserved", C.c_int32), ("topic_names", C.POINTER(C.c_char_p)),
+                ("partition_topic", C.POINTER(C.c_int32)), ("partition_number", C.POINTER(C.c_int32)),
+                ("replica_offset", C.POINTER(C.c_int32)), ("replica_broker_id", C.POINTER(C.c_int32)),
+                ("leader_broker_id", C.POINTER(C.c_int32)), ("replica_offline", C.POINTER(C.c_uint8)),
+                ("replica_logdir", C.POINTER(C.c_int32)), ("logdir_names", C.POINTER(C.c_char_p))]
+
+
 # ccmi_aggregation_function, ccmi_extrapolation (Extrapolation.java order), ccmi_granularity, ccmi_aggregation_failure
 AGG_AVG, AGG_MAX, AGG_LATEST = range(3)
 EXTRAPOLATIONS = ("NONE", "AVG_AVAILABLE", "AVG_ADJACENT", "FORCED_INSUFFICIENT", "NO_VALID_EXTRAPOLATION")
@@ -391,7 +400,7 @@ EXPORTED_SYMBOLS = (
     "ccmi_builder_desc", "ccmi_builder_broker_ids",
     "ccmi_aggregator_create", "ccmi_aggregator_destroy", "ccmi_aggregator_add_samples", "ccmi_aggregator_state_query",
     "ccmi_aggregator_completeness_query", "ccmi_aggregator_aggregate", "ccmi_aggregator_peek_current_window",
-    "ccmi_aggregator_remove_entities", "ccmi_aggregator_clear")
+    "ccmi_aggregator_remove_entities", "ccmi_aggregator_clear", "ccmi_builder_populate_from_aggregator")
 
 # int (*)(void* ctx, int64_t* key): replace *key by the MIN over all shards, return 0 (include/ccmi.h)
 AllreduceMinFn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int64))
@@ -488,6 +497,15 @@ class Library:
                                                               C.POINTER(C.c_int64)]
             L.ccmi_aggregator_remove_entities.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
             L.ccmi_aggregator_clear.argtypes = [C.c_void_p]
+        # LoadMonitor.clusterModel's bulk load from an aggregator's device rows (K18): device only as well
+        self.has_load_model = hasattr(L, "ccmi_builder_populate_from_aggregator")
+        if self.has_load_model:
+            L.ccmi_builder_populate_from_aggregator.argtypes = [
+                C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(AggregationOptionsStruct), C.c_void_p,
+                C.POINTER(C.c_int32), C.POINTER(PartitionTopologyStruct), C.POINTER(AggregatorCompletenessStruct),
+                C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+            if hasattr(L, "ccmi_load_model_timing"):  # diagnostics, outside the ABI (csrc/ccmi_load_model.cpp)
+                L.ccmi_load_model_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.ccmi_session_apply.argtypes = [C.c_void_p, C.POINTER(ActionStruct), C.c_int64, C.POINTER(C.c_int64)]
         # diagnostics, outside the ABI (csrc/ccmi_session.h)
         self.has_queue_probe = hasattr(L, "ccmi_queue_probe")
@@ -1559,6 +1577,38 @@ class LoadMonitorModel:
             -1 if leader is None else leader, off, ld, (C.c_float * len(vals))(*vals)))
         self._desc = None
 
+    def populate_from_aggregator(self, agg: "MetricSampleAggregator", from_ms: int, to_ms: int,
+                                 options: "AggregationOptions", topology: "PartitionTopology", interested=None,
+                                 metric_of: Optional[Sequence[int]] = None) -> "AggregatorCompleteness":
+        """ccmi_builder_populate_from_aggregator: agg.aggregate(from_ms, to_ms, options, interested) and
+        populate_partition for every row of it in one device call; entity e of the aggregator is partition e of
+        `topology`. -> the aggregate's completeness, with `num_rows` (rows of the aggregate) and `num_populated`
+        (partitions added). `metric_of`: the aggregator's metric index of each of METRICS, by default their places in
+        KAFKA_COMMON_METRICS. On an error nothing is added."""
+        import numpy as np
+
+        if not self.lib.has_load_model:
+            raise UnsupportedOperationException(f"{self.lib.path} does not export "
+                                                "ccmi_builder_populate_from_aggregator: the bulk load runs on the "
+                                                "device only")
+        if metric_of is None:
+            names = [n for n, _ in KAFKA_COMMON_METRICS]
+            metric_of = [names.index(m) for m in self.METRICS]
+        if len(metric_of) != len(self.METRICS):
+            raise IllegalArgumentException("metric_of has one entry per builder metric")
+        s, arrays = agg._completeness_struct(np)
+        mask = agg._mask(np, interested)
+        o = options.struct()
+        rows, populated = C.c_int64(0), C.c_int64(0)
+        t = topology.struct()
+        self.lib.check(self.lib.lib.ccmi_builder_populate_from_aggregator(
+            self.handle, agg.handle, from_ms, to_ms, C.byref(o), mask.ctypes.data if mask is not None else None,
+            (C.c_int32 * len(metric_of))(*metric_of), C.byref(t), C.byref(s), C.byref(rows), C.byref(populated)))
+        self._desc = None
+        c = AggregatorCompleteness(np, s, arrays)
+        c.num_rows, c.num_populated = int(rows.value), int(populated.value)
+        return c
+
     def set_broker_state(self, broker_id: int, state: str) -> None:
         self.lib.check(self.lib.lib.ccmi_builder_set_broker_state(self.handle, broker_id, BROKER_STATES[state]))
         self._desc = None
@@ -1627,6 +1677,49 @@ class AggregatorCompleteness:
         self.valid_entity_ratio = np.float32(s.valid_entity_ratio)
         self.valid_entity_group_ratio = np.float32(s.valid_entity_group_ratio)
         self.valid_entities, self.valid_groups = valid_entities, valid_groups  # uint8 masks, completeness() only
+
+
+class PartitionTopology:
+    """ccmi_partition_topology: what Cluster.partition(tp) answers for every entity of a partition aggregator, as numpy
+    arrays plus the name lists. Partition e has topic topic_names[partition_topic[e]], number partition_number[e], the
+    replica brokers replica_broker_id[replica_offset[e]:replica_offset[e + 1]] in PartitionInfo.replicas() order (an
+    empty range: the partition is unknown to the metadata and is skipped) and the leader leader_broker_id[e] (-1: offline).
+    replica_offline (bytes) and replica_logdir (indices into logdir_names, -1 = none) are optional."""
+
+    def __init__(self, topic_names: Sequence[str], partition_topic, partition_number, replica_offset, replica_broker_id,
+                 leader_broker_id, replica_offline=None, replica_logdir=None, logdir_names: Sequence[str] = ()):
+        import numpy as np
+
+        def arr(a, dtype):
+            return None if a is None else np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+
+        self.topic_names, self.logdir_names = [str(n) for n in topic_names], [str(n) for n in logdir_names]
+        self.partition_topic, self.partition_number = arr(partition_topic, np.int32), arr(partition_number, np.int32)
+        self.replica_offset, self.replica_broker_id = arr(replica_offset, np.int32), arr(replica_broker_id, np.int32)
+        self.leader_broker_id = arr(leader_broker_id, np.int32)
+        self.replica_offline, self.replica_logdir = arr(replica_offline, np.uint8), arr(replica_logdir, np.int32)
+        P = int(self.partition_topic.size)
+        R = int(self.replica_broker_id.size)
+        if self.partition_number.size != P or self.leader_broker_id.size != P or self.replica_offset.size != P + 1:
+            raise IllegalArgumentException("the per-partition arrays disagree on the number of partitions")
+        if int(self.replica_offset[-1]) != R or any(a is not None and a.size != R
+                                                    for a in (self.replica_offline, self.replica_logdir)):
+            raise IllegalArgumentException("the per-replica arrays disagree with replica_offset")
+        self.num_partitions, self.num_replicas = P, R
+
+    def struct(self) -> PartitionTopologyStruct:
+        """The C struct over this object's arrays (which it keeps alive: hold the object while the struct is in use)."""
+        def ptr(a, ctype):
+            return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
+
+        self._topic_c = (C.c_char_p * max(1, len(self.topic_names)))(*[n.encode() for n in self.topic_names])
+        self._logdir_c = (C.c_char_p * max(1, len(self.logdir_names)))(*[n.encode() for n in self.logdir_names])
+        return PartitionTopologyStruct(
+            self.num_partitions, len(self.topic_names), len(self.logdir_names), 0, self._topic_c,
+            ptr(self.partition_topic, C.c_int32), ptr(self.partition_number, C.c_int32),
+            ptr(self.replica_offset, C.c_int32), ptr(self.replica_broker_id, C.c_int32),
+            ptr(self.leader_broker_id, C.c_int32), ptr(self.replica_offline, C.c_uint8),
+            ptr(self.replica_logdir, C.c_int32), self._logdir_c if self.logdir_names else None)
 
 
 class AggregationResult:

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "ccmi.h"
+#include "ccmi_aggregator_impl.h"
 #include "ccmi_session.h"
 #include "engine/aggregator.h"
 #include "engine/aggregator_entity.h"
@@ -24,27 +25,10 @@ static_assert(sizeof(ccmi_aggregator_config) == 32 && sizeof(ccmi_aggregator_sta
 
 namespace {
 
+using ccmi::AggDeviceRows;
+using ccmi::align256;
 using ccmi::hipCheck;
-
-// a device buffer that only grows
-struct DBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  void* ensure(size_t bytes) {
-    if (bytes > cap) {
-      if (p) (void)hipFree(p);
-      p = nullptr;
-      cap = 0;
-      const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-      hipCheck(hipMalloc(&p, want), "hipMalloc (aggregator)");
-      cap = want;
-    }
-    return p;
-  }
-  ~DBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
+using ccmi::WalkResult;
 
 const float kJavaNaN = [] {  // Float.NaN, the result of Java's 0f / 0
   const uint32_t bits = 0x7fc00000u;
@@ -62,34 +46,6 @@ float ratio(unsigned long long n, unsigned long long total) {  // (float) n / to
 long long windowIndexOf(long long timeMs, long long windowMs) {
   return (long long)((unsigned long long)(timeMs / windowMs) + 1ull);
 }
-
-}  // namespace
-
-struct ccmi_aggregator {
-  int device = 0;
-  hipStream_t st = nullptr;
-  ccmi_aggregator_config cfg{};
-  ccmi::AggTables T{};
-  ccmi::AggWalk W{};
-  long long current = 0, oldest = 0, generation = 0;  // _currentWindowIndex, _oldestWindowIndex, _generation
-  DBuf state, walk, batch, rows, small;
-
-  ~ccmi_aggregator() {
-    if (st) (void)hipStreamDestroy(st);
-  }
-  int L() const { return cfg.num_windows + 1; }
-  void sync() { hipCheck(hipStreamSynchronize(st), "hipStreamSynchronize (aggregator)"); }
-  void up(void* dst, const void* src, size_t bytes) {
-    if (bytes) hipCheck(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync (aggregator, up)");
-  }
-  void down(void* dst, const void* src, size_t bytes) {
-    if (bytes) hipCheck(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st), "hipMemcpyAsync (aggregator, down)");
-  }
-};
-
-namespace {
-
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // carves `bytes` out of a block, 256-byte aligned
 struct Carver {
@@ -138,15 +94,6 @@ void checkOptions(const ccmi_aggregation_options* o) {
   if (o->granularity != CCMI_GRANULARITY_ENTITY && o->granularity != CCMI_GRANULARITY_ENTITY_GROUP)
     throw std::invalid_argument("unknown granularity");
 }
-
-// What a walk left on the device, read back once.
-struct WalkResult {
-  bool inRange = false;
-  int numWindows = 0;
-  long long firstWindow = 0;
-  std::vector<unsigned long long> ctr;
-  std::vector<long long> validWindows;  // newest first
-};
 
 // MetricSampleAggregator.completeness: clamps the range, runs the walk, fills `out` (and the two masks when given).
 WalkResult runCompleteness(ccmi_aggregator& a, int64_t fromMs, int64_t toMs, const ccmi_aggregation_options& o,
@@ -213,9 +160,28 @@ WalkResult runCompleteness(ccmi_aggregator& a, int64_t fromMs, int64_t toMs, con
   return r;
 }
 
-// Compacts the covered entities (source: 0 interested, 1 valid, 2 present) and writes the rows below `capacity`.
+// ccmi_aggregator_impl.h's aggRowsOnDevice, then the rows copied into the caller's arrays.
 int64_t runRows(ccmi_aggregator& a, int source, const std::vector<long long>& windows, int maxExtrapolations,
                 int64_t capacity, int32_t* entities, float* values, uint8_t* extrapolations, uint8_t* invalid) {
+  const int M = a.cfg.num_metrics, Wv = (int)windows.size();
+  const AggDeviceRows d = ccmi::aggRowsOnDevice(a, source, windows, maxExtrapolations, capacity, invalid != nullptr);
+  const int64_t k = d.k;
+  if (k <= 0) return d.covered;
+  if (!entities || !values || !extrapolations) throw std::invalid_argument("null row array with capacity > 0");
+  a.down(entities, d.entities, sizeof(int32_t) * (size_t)k);
+  a.down(values, d.values, sizeof(float) * (size_t)k * M * Wv);
+  a.down(extrapolations, d.extrapolations, (size_t)k * Wv);
+  if (invalid) a.down(invalid, d.invalid, (size_t)k);
+  a.sync();
+  return d.covered;
+}
+
+}  // namespace
+
+namespace ccmi {
+
+AggDeviceRows aggRowsOnDevice(ccmi_aggregator& a, int source, const std::vector<long long>& windows,
+                              int maxExtrapolations, int64_t capacity, bool wantInvalid) {
   const int E = a.cfg.num_entities, M = a.cfg.num_metrics, Wv = (int)windows.size();
   const int tiles = (E + ccmi::kAggTile - 1) / ccmi::kAggTile;
   char* sm = (char*)a.small.ensure(align256((size_t)E) + 4096 + align256(sizeof(uint32_t) * ((size_t)tiles + 1)) +
@@ -226,28 +192,53 @@ int64_t runRows(ccmi_aggregator& a, int source, const std::vector<long long>& wi
   unsigned long long covered = 0;
   a.down(&covered, a.W.ctr + ccmi::kAcCovered, sizeof(covered));
   a.sync();
+  AggDeviceRows d;
+  d.covered = (int64_t)covered;
   const int64_t k = std::min<int64_t>(capacity, (int64_t)covered);
-  if (k <= 0) return (int64_t)covered;
-  if (!entities || !values || !extrapolations) throw std::invalid_argument("null row array with capacity > 0");
+  if (k <= 0) return d;
+  d.k = k;
   const size_t bEnt = align256(sizeof(int32_t) * (size_t)k), bVal = align256(sizeof(float) * (size_t)k * M * Wv),
                bEx = align256((size_t)k * Wv), bInv = align256((size_t)k);
   char* rb = (char*)a.rows.ensure(bEnt + bVal + bEx + bInv);
-  int32_t* dEnt = (int32_t*)rb;
-  float* dVal = (float*)(rb + bEnt);
-  uint8_t* dEx = (uint8_t*)(rb + bEnt + bVal);
-  uint8_t* dInv = (uint8_t*)(rb + bEnt + bVal + bEx);
+  d.entities = (int32_t*)rb;
+  d.values = (float*)(rb + bEnt);
+  d.extrapolations = (uint8_t*)(rb + bEnt + bVal);
+  d.invalid = (uint8_t*)(rb + bEnt + bVal + bEx);
   a.up(dWindows, windows.data(), sizeof(long long) * (size_t)Wv);
-  ccmi::aggLaunchRows(a.T, a.W, source, dTileOff, dWindows, Wv, a.oldest, maxExtrapolations, k, dEnt, dVal, dEx,
-                      invalid ? dInv : nullptr, a.st);
-  a.down(entities, dEnt, sizeof(int32_t) * (size_t)k);
-  a.down(values, dVal, sizeof(float) * (size_t)k * M * Wv);
-  a.down(extrapolations, dEx, (size_t)k * Wv);
-  if (invalid) a.down(invalid, dInv, (size_t)k);
-  a.sync();
-  return (int64_t)covered;
+  ccmi::aggLaunchRows(a.T, a.W, source, dTileOff, dWindows, Wv, a.oldest, maxExtrapolations, k, d.entities, d.values,
+                      d.extrapolations, wantInvalid ? d.invalid : nullptr, a.st);
+  return d;
 }
 
-}  // namespace
+bool aggPrepareAggregate(ccmi_aggregator& a, int64_t fromMs, int64_t toMs, const ccmi_aggregation_options& o,
+                         const uint8_t* interested, ccmi_aggregator_completeness* out, WalkResult* walk) {
+  *walk = runCompleteness(a, fromMs, toMs, o, interested, out, nullptr, nullptr);
+  if (!walk->inRange) {
+    out->failure = CCMI_AGG_FAILURE_NO_WINDOW_IN_RANGE;
+    return false;
+  }
+  // validateCompleteness
+  if (out->num_valid_windows < o.min_valid_windows) {
+    out->failure = CCMI_AGG_FAILURE_NOT_ENOUGH_VALID_WINDOWS;
+    return false;
+  }
+  char msg[256];
+  if ((double)out->valid_entity_ratio < o.min_valid_entity_ratio) {
+    std::snprintf(msg, sizeof(msg), "The entity coverage %.3f in range [%lld, %lld] does not meet requirement.",
+                  (double)out->valid_entity_ratio, (long long)fromMs, (long long)toMs);
+    throw ccmi::StateError(msg);
+  }
+  if ((double)out->valid_entity_group_ratio < o.min_valid_entity_group_ratio) {
+    std::snprintf(msg, sizeof(msg), "The entity group coverage %.3f in range [%lld, %lld] does not meet requirement.",
+                  (double)out->valid_entity_group_ratio, (long long)fromMs, (long long)toMs);
+    throw ccmi::StateError(msg);
+  }
+  return true;
+}
+
+void aggCheckOptions(const ccmi_aggregation_options* o) { checkOptions(o); }
+
+}  // namespace ccmi
 
 extern "C" ccmi_status ccmi_aggregator_create(int32_t device_ordinal, const ccmi_aggregator_config* config,
                                               const uint8_t* metric_function, const int32_t* entity_group,
@@ -424,27 +415,8 @@ extern "C" ccmi_status ccmi_aggregator_aggregate(ccmi_aggregator* a, int64_t fro
     checkOptions(options);
     *num_entities = 0;
     const ccmi::DeviceGuard dg(a->device);
-    const WalkResult r = runCompleteness(*a, from_ms, to_ms, *options, interested, out, nullptr, nullptr);
-    if (!r.inRange) {
-      out->failure = CCMI_AGG_FAILURE_NO_WINDOW_IN_RANGE;
-      return CCMI_OK;
-    }
-    // validateCompleteness
-    if (out->num_valid_windows < options->min_valid_windows) {
-      out->failure = CCMI_AGG_FAILURE_NOT_ENOUGH_VALID_WINDOWS;
-      return CCMI_OK;
-    }
-    char msg[256];
-    if ((double)out->valid_entity_ratio < options->min_valid_entity_ratio) {
-      std::snprintf(msg, sizeof(msg), "The entity coverage %.3f in range [%lld, %lld] does not meet requirement.",
-                    (double)out->valid_entity_ratio, (long long)from_ms, (long long)to_ms);
-      throw ccmi::StateError(msg);
-    }
-    if ((double)out->valid_entity_group_ratio < options->min_valid_entity_group_ratio) {
-      std::snprintf(msg, sizeof(msg), "The entity group coverage %.3f in range [%lld, %lld] does not meet requirement.",
-                    (double)out->valid_entity_group_ratio, (long long)from_ms, (long long)to_ms);
-      throw ccmi::StateError(msg);
-    }
+    WalkResult r;
+    if (!ccmi::aggPrepareAggregate(*a, from_ms, to_ms, *options, interested, out, &r)) return CCMI_OK;
     *num_entities = runRows(*a, options->include_invalid_entities ? 0 : 1, r.validWindows,
                             options->max_allowed_extrapolations_per_entity, capacity, entities, values, extrapolations,
                             invalid);

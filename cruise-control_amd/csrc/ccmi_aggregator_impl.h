@@ -1,0 +1,114 @@
+// What the two translation units behind ccmi_aggregator share (ccmi_aggregator.cpp, ccmi_load_model.cpp): the
+// aggregator object and the two steps of an aggregate that leave their result on the device. Private to the library;
+// include/ccmi.h only names the struct.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "ccmi.h"
+#include "engine/aggregator.h"
+#include "engine/hip_check.h"
+
+namespace ccmi {
+
+inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// a device buffer that only grows
+struct DBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  void* ensure(size_t bytes) {
+    if (bytes > cap) {
+      if (p) (void)hipFree(p);
+      p = nullptr;
+      cap = 0;
+      const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
+      ccmi::hipCheck(hipMalloc(&p, want), "hipMalloc (aggregator)");
+      cap = want;
+    }
+    return p;
+  }
+  ~DBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+// a pinned host buffer that only grows: the staging of K18's one copy in and one copy out
+struct HBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  void* ensure(size_t bytes) {
+    if (bytes > cap) {
+      if (p) (void)hipHostFree(p);
+      p = nullptr;
+      cap = 0;
+      const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
+      ccmi::hipCheck(hipHostMalloc(&p, want, hipHostMallocDefault), "hipHostMalloc (aggregator)");
+      cap = want;
+    }
+    return p;
+  }
+  ~HBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+};
+
+}  // namespace ccmi
+
+struct ccmi_aggregator {
+  int device = 0;
+  hipStream_t st = nullptr;
+  ccmi_aggregator_config cfg{};
+  ccmi::AggTables T{};
+  ccmi::AggWalk W{};
+  long long current = 0, oldest = 0, generation = 0;  // _currentWindowIndex, _oldestWindowIndex, _generation
+  ccmi::DBuf state, walk, batch, rows, small;
+  ccmi::HBuf pinUp, pinDown;   // K18: pinned staging of the topology going up and of the columns coming down
+  ccmi::DBuf loadIn, loadOut;  // K18 (ccmi_load_model.cpp): the uploaded topology and per-row scratch, the builder columns
+  double loadTiming[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the last bulk load's split (ccmi_load_model_timing)
+
+  ~ccmi_aggregator() {
+    if (st) (void)hipStreamDestroy(st);
+  }
+  int L() const { return cfg.num_windows + 1; }
+  void sync() { ccmi::hipCheck(hipStreamSynchronize(st), "hipStreamSynchronize (aggregator)"); }
+  void up(void* dst, const void* src, size_t bytes) {
+    if (bytes) ccmi::hipCheck(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st), "hipMemcpyAsync (aggregator, up)");
+  }
+  void down(void* dst, const void* src, size_t bytes) {
+    if (bytes) ccmi::hipCheck(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st), "hipMemcpyAsync (aggregator, down)");
+  }
+};
+
+namespace ccmi {
+
+// What a walk left on the device, read back once.
+struct WalkResult {
+  bool inRange = false;
+  int numWindows = 0;
+  long long firstWindow = 0;
+  std::vector<unsigned long long> ctr;
+  std::vector<long long> validWindows;  // newest first
+};
+
+// The rows of an aggregate as agg_rows left them in a.rows (valid until the aggregator's next call).
+struct AggDeviceRows {
+  int64_t covered = 0, k = 0;  // the covered entities and how many of them have a row: min(capacity, covered)
+  int32_t* entities = nullptr;
+  float* values = nullptr;  // [k][M][Wv]
+  uint8_t *extrapolations = nullptr, *invalid = nullptr;
+};
+
+// checkOptions of the aggregator's calls: std::invalid_argument for a null or malformed options struct
+void aggCheckOptions(const ccmi_aggregation_options* o);
+// ccmi_aggregator_aggregate up to validateCompleteness: fills `out`; false when out->failure is set (no rows).
+bool aggPrepareAggregate(ccmi_aggregator& a, int64_t fromMs, int64_t toMs, const ccmi_aggregation_options& o,
+                         const uint8_t* interested, ccmi_aggregator_completeness* out, WalkResult* walk);
+// Compacts the covered entities (source: 0 interested, 1 valid, 2 present) and writes the rows below `capacity` into
+// a.rows. Synchronises once (the covered count); the rows kernel is only enqueued.
+AggDeviceRows aggRowsOnDevice(ccmi_aggregator& a, int source, const std::vector<long long>& windows,
+                              int maxExtrapolations, int64_t capacity, bool wantInvalid);
+
+}  // namespace ccmi

@@ -35,4 +35,53 @@ void aggLaunchStateSums(const AggTables& T, unsigned long long* sums, hipStream_
 // clears the state of ids[n] that are present; *removed becomes nonzero if any was (removed is cleared here)
 void aggLaunchRemove(const AggTables& T, const int32_t* ids, int64_t n, uint32_t* removed, hipStream_t st);
 
+// ---- K18 (kernels/load_model.hip): MonitorUtils.populatePartitionLoad over the rows aggLaunchRows left on the device,
+// as ccmi_builder_populate_from_aggregator (ccmi_load_model.cpp) calls it. All pointers are device memory.
+struct LoadTopology {  // ccmi_partition_topology, uploaded; entity e = partition e
+  const int32_t* topic;          // [P]
+  const int32_t* number;         // [P]
+  const int32_t* replicaOffset;  // [P + 1], non-decreasing from 0, at most 8 apart (checked on the host)
+  const int32_t* replicaBroker;  // [R] Kafka ids
+  const int32_t* leader;         // [P] Kafka id, negative = offline partition
+  const uint8_t* offline;        // [R] or null
+  const int32_t* logdir;         // [R] or null
+  const int32_t* knownBrokers;   // [numKnown] the builder's broker ids, ascending
+  int32_t numKnown;
+};
+struct LoadRows {  // the aggregate's rows: entities ascending, values [k][M][W]
+  const int32_t* entities;
+  const float* values;
+  long long k;
+  int32_t M, W;
+  int32_t metricOf[6];  // the aggregator metric of each ccmi_metric
+};
+enum : int { kLoadErrUnknownBroker = 1, kLoadErrDuplicateBroker = 2, kLoadErrLeader = 3 };
+enum : int { kLoadStateError = 0, kLoadStatePartitions = 1, kLoadStateReplicas = 2, kLoadStateWords = 4 };
+constexpr unsigned long long kLoadNoError = ~0ull;
+struct LoadScratch {
+  uint32_t* kept;             // [k] replicas of a row's partition when it is populated, else 0
+  uint8_t* leaderIdx;         // [k] the leader's position among the replicas
+  uint32_t* rank;             // [k] populated partitions before the row
+  uint32_t* replicaBase;      // [k] their replicas
+  unsigned long long* state;  // [kLoadStateWords]: (entity << 2 | code) of the lowest failing entity or kLoadNoError, the
+                              // populated partitions, their replicas
+};
+struct LoadColumns {  // the builder's columns for this call's partitions [P'] and replicas [R'], in populate order
+  int32_t *pTopic, *pNumber, *pEnd;  // topic as the topology numbers it; pEnd = baseReplica + the range's end
+  int32_t *rBroker, *rPartition;     // rPartition = basePartition + rank
+  uint8_t *rLeader, *rOffline;
+  int32_t* rLogdir;                  // index into the topology's logdir names, -1 = none
+  unsigned long long* rDesc;         // device only: row << 16 | n << 8 | leaderIdx << 4 | idx
+  float* load;                       // [R'][6][W]
+  int32_t basePartition, baseReplica;
+};
+// classify (one lane per row: broker, duplicate and leader checks, the kept replica count, the first error by an
+// atomic min) and offsets (exclusive scan of the kept flags and counts); S.state is set here. Enqueues only.
+void loadLaunchClassify(const LoadTopology& T, const LoadRows& R, const LoadScratch& S, hipStream_t st);
+// the compacted partition and replica columns, one lane per row
+void loadLaunchColumns(const LoadTopology& T, const LoadRows& R, const LoadScratch& S, const LoadColumns& C,
+                       hipStream_t st);
+// C.load through engine/replica_load.h, tiles of whole replicas staged in LDS; numReplicas = state[kLoadStateReplicas]
+void loadLaunchLoads(const LoadRows& R, const LoadColumns& C, long long numReplicas, hipStream_t st);
+
 }  // namespace ccmi

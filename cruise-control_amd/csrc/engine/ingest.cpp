@@ -18,6 +18,7 @@
 
 #include "ccmi.h"
 #include "errors.h"  // setLastError (ccmi_last_error)
+#include "model_builder.h"
 
 namespace {
 
@@ -26,45 +27,10 @@ constexpr double kCpuWeightLeaderBytesIn = 0.7;             // ModelParameters d
 constexpr double kCpuWeightLeaderBytesOut = 0.15;
 constexpr double kCpuWeightFollowerBytesIn = 0.15;
 
-struct BrokerIn {
-  int32_t id;
-  int32_t rack;
-  double cap[4];
-  int32_t state;
-  std::string host;  // Rack._hosts key (handleDeadBroker: "UNKNOWN_HOST-<n>", a host of its own)
-};
-struct DiskIn {
-  int32_t brokerId;
-  std::string logdir;
-  double cap;
-  uint8_t demoted = 0;
-};
+using ccmi::ingest::BrokerIn;
+using ccmi::ingest::DiskIn;
 
 }  // namespace
-
-struct ccmi_model_builder {
-  int32_t W = 1;
-  std::vector<std::string> rackNames;
-  std::map<std::string, int32_t> rackIndex;
-  std::vector<BrokerIn> brokers;  // creation order
-  std::map<int32_t, size_t> brokerById;
-  std::vector<DiskIn> disks;
-  std::vector<std::string> topics;
-  std::map<std::string, int32_t> topicIndex;
-  // partitions / replicas in populate order
-  std::vector<int32_t> pTopic, pNumber, pOff{0};
-  std::vector<int32_t> rBrokerId, rPartition;
-  std::vector<uint8_t> rLeader, rOffline;
-  std::vector<std::string> rLogdir;  // "" = none
-  std::vector<float> rLoad;          // [R][6][W]
-  // flattened output (ccmi_builder_desc)
-  std::vector<int32_t> oBrokerId, oRack, oState, oRBroker, oPartReplicas, oDiskBroker, oRDisk, oHost;
-  std::vector<uint8_t> oDiskDemoted;
-  int32_t unknownHosts = 0;
-  std::vector<double> oCap, oDiskCap;
-  std::vector<const char*> oTopicNames, oDiskLogdir;
-  std::vector<int32_t> sortedIds;
-};
 
 namespace {
 

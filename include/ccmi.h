@@ -42,6 +42,10 @@
  *   ccmi_aggregator_*          <- MetricSampleAggregator.addSample / completeness / aggregate / peekCurrentWindow
  *                                 cruise-control-core monitor/sampling/aggregator/MetricSampleAggregator.java:141-293,
  *                                 RawMetricValues.java, WindowState.java (the step before ccmi_builder_populate_partition)
+ *   ccmi_builder_populate_from_aggregator
+ *                              <- MonitorUtils.populatePartitionLoad for every partition of an aggregate
+ *                                 monitor/LoadMonitor.java:491-543, monitor/MonitorUtils.java:415-479 (one device call
+ *                                 from the aggregator's rows to the model builder)
  *   ccmi_random_cluster        <- test fixture RandomCluster.generate+populate
  *                                 (src/test/java/.../model/RandomCluster.java:53-455)
  *
@@ -1057,6 +1061,55 @@ ccmi_status ccmi_aggregator_peek_current_window(ccmi_aggregator* a, int32_t* ent
                                                 int64_t capacity, int64_t* num_entities);
 ccmi_status ccmi_aggregator_remove_entities(ccmi_aggregator* a, const int32_t* entities /* [n] */, int64_t n);
 ccmi_status ccmi_aggregator_clear(ccmi_aggregator* a);
+
+/*
+ * ccmi_builder_populate_from_aggregator, additive at ABI v13: the capability flag is the presence of the symbol. The
+ * seam between the two halves of LoadMonitor.clusterModel (monitor/LoadMonitor.java:491-543) in one call: the
+ * aggregate of `a` over [from_ms, to_ms] with `options` and `interested`, and MonitorUtils.populatePartitionLoad
+ * (monitor/MonitorUtils.java:415-479) for every row of it. The rows never leave the device on the way: the validity
+ * checks, the compaction of the partitions that are populated and the replica loads run there (K18), the finished
+ * columns come back in one copy and are appended to the builder.
+ *
+ * Entity e of the aggregator is partition e of `topology` (Cluster.partition(tp)); metric_of[m] is the aggregator's
+ * metric index of ccmi_metric m ({0, 1, 2, 3, 7, 8} for KafkaMetricDef's common metrics).
+ *
+ * Contract: the builder ends in exactly the state it would reach from ccmi_aggregator_aggregate (same range, options
+ * and mask, with capacity for every row) followed by one ccmi_builder_populate_partition per returned row in ascending
+ * entity order. Every returned row is populated, the zero rows of absent entities under include_invalid_entities
+ * included. A partition with an empty replica range (partitionInfo == null, its topic was deleted) is left out. An
+ * offline partition (leader_broker_id < 0) is checked for unknown and duplicate brokers and then skipped. A second
+ * call appends; topics keep first-appearance order across calls. `out` is filled as ccmi_aggregator_aggregate fills
+ * it; NotEnoughValidWindows, or no window in range, is CCMI_OK with out->failure set and nothing populated.
+ * *num_rows is the number of rows of the aggregate, *num_populated the partitions added to the builder.
+ *
+ * Errors, CCMI_E_INVALID with the text in ccmi_last_error: a NULL argument that is not marked nullable; num_partitions
+ * other than the aggregator's E; a metric_of entry, topic index or logdir index out of range; a replica_offset that
+ * does not start at 0 or decreases; more than 8 replicas in one partition; out->num_valid_windows other than the
+ * builder's W; and the three complaints of ccmi_builder_populate_partition in its words (a replica on an unknown
+ * broker, a duplicate replica broker, a leader that is not one of the replica brokers). Those three are raised only
+ * for partitions that are rows of the aggregate, and for the lowest such entity id. On any error the builder is
+ * unchanged. That is stricter than the per-row loop, which keeps the partitions it populated before the bad one.
+ * CCMI_E_DEVICE for a device failure.
+ */
+typedef struct ccmi_partition_topology {      /* Cluster.partition(tp) for entity e = partition e of the aggregator */
+  int32_t num_partitions, num_topics, num_logdirs, reserved;
+  const char* const* topic_names;             /* [num_topics] */
+  const int32_t* partition_topic;             /* [P] index into topic_names */
+  const int32_t* partition_number;            /* [P] */
+  const int32_t* replica_offset;              /* [P + 1]; an empty range = partitionInfo == null (topic deleted): skipped */
+  const int32_t* replica_broker_id;           /* [R] Kafka ids in PartitionInfo.replicas() order */
+  const int32_t* leader_broker_id;            /* [P]; -1 = offline partition */
+  const uint8_t* replica_offline;             /* nullable [R] */
+  const int32_t* replica_logdir;              /* nullable [R] index into logdir_names, -1 = none */
+  const char* const* logdir_names;            /* nullable [num_logdirs] */
+} ccmi_partition_topology;
+
+ccmi_status ccmi_builder_populate_from_aggregator(
+    ccmi_model_builder* b, ccmi_aggregator* a, int64_t from_ms, int64_t to_ms,
+    const ccmi_aggregation_options* options, const uint8_t* interested /* nullable [E] */,
+    const int32_t metric_of[6] /* aggregator metric index of each ccmi_metric, e.g. {0,1,2,3,7,8} */,
+    const ccmi_partition_topology* topology, ccmi_aggregator_completeness* out,
+    int64_t* num_rows /* rows of the aggregate */, int64_t* num_populated /* partitions added to the builder */);
 
 /*
  * Destination-sharded mode (one process per GPU): every rank creates a session on its own device from the same
