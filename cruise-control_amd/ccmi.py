@@ -328,6 +328,48 @@ class PartitionTopologyStruct(C.Structure):  # ccmi_partition_topology, 88 bytes
                 ("replica_logdir", C.POINTER(C.c_int32)), ("logdir_names", C.POINTER(C.c_char_p))]
 
 
+class MetricAnomalyConfigStruct(C.Structure):  # ccmi_metric_anomaly_config, 32 bytes
+    _fields_ = [("upper_percentile", C.c_double), ("lower_percentile", C.c_double), ("upper_margin", C.c_double),
+                ("lower_margin", C.c_double)]
+
+
+class MetricAnomalyStruct(C.Structure):  # ccmi_metric_anomaly, 32 bytes
+    _fields_ = [("entity", C.c_int32), ("metric", C.c_int32), ("current", C.c_double),
+                ("upper_threshold", C.c_double), ("lower_threshold", C.c_double)]
+
+
+class SlowBrokerConfigStruct(C.Structure):  # ccmi_slow_broker_config, 80 bytes
+    _fields_ = [("bytes_in_rate_detection_threshold", C.c_double), ("log_flush_time_threshold_ms", C.c_double),
+                ("metric_history_percentile", C.c_double), ("metric_history_margin", C.c_double),
+                ("peer_metric_percentile", C.c_double), ("peer_metric_margin", C.c_double),
+                ("self_healing_unfixable_ratio", C.c_double), ("demotion_score", C.c_int32),
+                ("decommission_score", C.c_int32), ("log_flush_metric", C.c_int32),
+                ("leader_bytes_in_metric", C.c_int32), ("replication_bytes_in_metric", C.c_int32),
+                ("removal_enabled", C.c_int32)]
+
+
+class SlowBrokerSummaryStruct(C.Structure):  # ccmi_slow_broker_summary, 72 bytes
+    _fields_ = [("current_window_index", C.c_int64), ("peer_base_log_flush", C.c_double),
+                ("peer_base_per_byte", C.c_double), ("num_current", C.c_int32), ("num_skipped", C.c_int32),
+                ("num_active", C.c_int32), ("cluster_size", C.c_int32), ("num_persistent", C.c_int32),
+                ("num_recent", C.c_int32), ("num_suspect", C.c_int32), ("num_to_demote", C.c_int32),
+                ("num_to_remove", C.c_int32), ("unfixable", C.c_int32), ("removal_enabled", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class SlowBrokerStruct(C.Structure):  # ccmi_slow_broker, 24 bytes
+    _fields_ = [("entity", C.c_int32), ("kind", C.c_int32), ("score", C.c_int32), ("reserved", C.c_int32),
+                ("since_ms", C.c_int64)]
+
+
+SLOW_BROKER_DEMOTE, SLOW_BROKER_REMOVE = 1, 2  # ccmi_slow_broker.kind
+# CCMI_SLOW_DIAG_*: the bits of ccmi_slow_broker_finder_detect's per-entity diagnostic byte
+(SLOW_DIAG_SKIPPED, SLOW_DIAG_FLUSH_HISTORY, SLOW_DIAG_FLUSH_PEERS, SLOW_DIAG_PER_BYTE_HISTORY,
+ SLOW_DIAG_PER_BYTE_PEERS, SLOW_DIAG_OVER_THRESHOLD, SLOW_DIAG_SUSPECT) = 1, 2, 4, 8, 16, 32, 64
+ANOMALY_SYMBOLS = ("ccmi_aggregator_metric_anomalies", "ccmi_slow_broker_finder_create",
+                   "ccmi_slow_broker_finder_destroy", "ccmi_slow_broker_finder_detect",
+                   "ccmi_slow_broker_finder_scores", "ccmi_slow_broker_finder_reset")
+
 # ccmi_aggregation_function, ccmi_extrapolation (Extrapolation.java order), ccmi_granularity, ccmi_aggregation_failure
 AGG_AVG, AGG_MAX, AGG_LATEST = range(3)
 EXTRAPOLATIONS = ("NONE", "AVG_AVAILABLE", "AVG_ADJACENT", "FORCED_INSUFFICIENT", "NO_VALID_EXTRAPOLATION")
@@ -400,7 +442,9 @@ EXPORTED_SYMBOLS = (
     "ccmi_builder_desc", "ccmi_builder_broker_ids",
     "ccmi_aggregator_create", "ccmi_aggregator_destroy", "ccmi_aggregator_add_samples", "ccmi_aggregator_state_query",
     "ccmi_aggregator_completeness_query", "ccmi_aggregator_aggregate", "ccmi_aggregator_peek_current_window",
-    "ccmi_aggregator_remove_entities", "ccmi_aggregator_clear", "ccmi_builder_populate_from_aggregator")
+    "ccmi_aggregator_remove_entities", "ccmi_aggregator_clear", "ccmi_builder_populate_from_aggregator",
+    "ccmi_aggregator_metric_anomalies", "ccmi_slow_broker_finder_create", "ccmi_slow_broker_finder_destroy",
+    "ccmi_slow_broker_finder_detect", "ccmi_slow_broker_finder_scores", "ccmi_slow_broker_finder_reset")
 
 # int (*)(void* ctx, int64_t* key): replace *key by the MIN over all shards, return 0 (include/ccmi.h)
 AllreduceMinFn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int64))
@@ -497,6 +541,23 @@ class Library:
                                                               C.POINTER(C.c_int64)]
             L.ccmi_aggregator_remove_entities.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
             L.ccmi_aggregator_clear.argtypes = [C.c_void_p]
+        # the metric anomaly finders over an aggregator's device rows (K19): all six symbols or none, device only
+        self.has_metric_anomalies = hasattr(L, "ccmi_aggregator_metric_anomalies")
+        if self.has_metric_anomalies:
+            L.ccmi_aggregator_metric_anomalies.argtypes = [
+                C.c_void_p, C.c_int64, C.c_int64, C.POINTER(AggregationOptionsStruct), C.c_void_p,
+                C.POINTER(MetricAnomalyConfigStruct), C.c_void_p, C.POINTER(AggregatorCompletenessStruct),
+                C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+            L.ccmi_slow_broker_finder_create.argtypes = [C.c_void_p, C.POINTER(SlowBrokerConfigStruct),
+                                                         C.POINTER(C.c_void_p)]
+            L.ccmi_slow_broker_finder_destroy.argtypes = [C.c_void_p]
+            L.ccmi_slow_broker_finder_destroy.restype = None
+            L.ccmi_slow_broker_finder_detect.argtypes = [
+                C.c_void_p, C.c_int64, C.c_int64, C.POINTER(AggregationOptionsStruct), C.c_void_p, C.c_int64,
+                C.POINTER(AggregatorCompletenessStruct), C.POINTER(SlowBrokerSummaryStruct), C.c_void_p, C.c_int64,
+                C.POINTER(C.c_int64), C.c_void_p]
+            L.ccmi_slow_broker_finder_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+            L.ccmi_slow_broker_finder_reset.argtypes = [C.c_void_p]
         # LoadMonitor.clusterModel's bulk load from an aggregator's device rows (K18): device only as well
         self.has_load_model = hasattr(L, "ccmi_builder_populate_from_aggregator")
         if self.has_load_model:
@@ -1900,6 +1961,150 @@ class MetricSampleAggregator:
 
     def clear(self) -> None:
         self.lib.check(self.lib.lib.ccmi_aggregator_clear(self.handle))
+
+    def metric_anomalies(self, to_ms: int, interested_metrics, upper_percentile: float = 95.0,
+                         lower_percentile: float = 2.0, upper_margin: float = 0.5, lower_margin: float = 0.2,
+                         from_ms: int = -1, options: Optional[AggregationOptions] = None, interested=None,
+                         capacity: Optional[int] = None) -> "MetricAnomalies":
+        """PercentileMetricAnomalyFinder.metricAnomalies over this (broker) aggregator on the device
+        (ccmi_aggregator_metric_anomalies): the history is aggregate(from_ms, to_ms, options, interested), by default
+        KafkaBrokerMetricSampleAggregator's (ratios 0.0 / 0.0, one valid window, ENTITY, valid entities only, from -1),
+        the current values are peek_current_window's. `interested_metrics` is a byte mask over the M metrics. The
+        percentile and margin defaults are AnomalyDetectorConfig's."""
+        import numpy as np
+
+        if not self.lib.has_metric_anomalies:
+            raise UnsupportedOperationException(f"{self.lib.path} does not export ccmi_aggregator_metric_anomalies: "
+                                                "the anomaly finders run on the device only")
+        s, arrays = self._completeness_struct(np)
+        mask = self._mask(np, interested)
+        metrics = np.ascontiguousarray(interested_metrics, dtype=np.uint8).reshape(-1)
+        if metrics.size != self.M:
+            raise IllegalArgumentException("the interested metrics mask has one byte per metric")
+        cap = self.E * int(np.count_nonzero(metrics)) if capacity is None else int(capacity)
+        rec = np.zeros(max(cap, 0), dtype=METRIC_ANOMALY_DTYPE)  # a negative capacity is the library's to refuse
+        o = (options or AggregationOptions(0.0, 0.0, 1, 5, GRANULARITY_ENTITY, False)).struct()
+        cfg = MetricAnomalyConfigStruct(float(upper_percentile), float(lower_percentile), float(upper_margin),
+                                        float(lower_margin))
+        n, window = C.c_int64(0), C.c_int64(0)
+        self.lib.check(self.lib.lib.ccmi_aggregator_metric_anomalies(
+            self.handle, from_ms, to_ms, C.byref(o), mask.ctypes.data if mask is not None else None, C.byref(cfg),
+            metrics.ctypes.data, C.byref(s), C.byref(window), rec.ctypes.data if cap else None, cap, C.byref(n)))
+        return MetricAnomalies(AggregatorCompleteness(np, s, arrays), int(window.value), int(n.value),
+                               rec[:max(0, min(cap, n.value))])
+
+
+def _record_dtype(struct):
+    """The numpy dtype of a ctypes record struct (explicit offsets, the struct's size)."""
+    import numpy as np
+
+    kinds = {C.c_int32: np.int32, C.c_int64: np.int64, C.c_double: np.float64}
+    return np.dtype({"names": [n for n, _ in struct._fields_], "formats": [kinds[t] for _, t in struct._fields_],
+                     "offsets": [getattr(struct, n).offset for n, _ in struct._fields_],
+                     "itemsize": C.sizeof(struct)})
+
+
+try:
+    METRIC_ANOMALY_DTYPE = _record_dtype(MetricAnomalyStruct)
+    SLOW_BROKER_DTYPE = _record_dtype(SlowBrokerStruct)
+except ImportError:  # numpy is needed only by the array-shaped calls
+    METRIC_ANOMALY_DTYPE = SLOW_BROKER_DTYPE = None
+
+
+class MetricAnomalies:
+    """What ccmi_aggregator_metric_anomalies returns: `completeness` of the history aggregate (its failure set when
+    there was none), `current_window_index`, `num_anomalies` (numAnomaliesOfType(RECENT)) and `records`, a numpy record
+    array (entity, metric, current, upper_threshold, lower_threshold) in ascending (entity, metric) order, the first
+    `capacity` of them."""
+
+    def __init__(self, completeness, current_window_index, num_anomalies, records):
+        self.completeness, self.current_window_index = completeness, current_window_index
+        self.num_anomalies, self.records = num_anomalies, records
+
+
+class SlowBrokerDetection:
+    """One ccmi_slow_broker_finder_detect: `completeness`, `summary` (SlowBrokerSummaryStruct), `num_brokers`,
+    `brokers` (numpy records entity, kind, score, since_ms; kind SLOW_BROKER_DEMOTE / SLOW_BROKER_REMOVE) and
+    `diagnostics` (uint8 [E] of SLOW_DIAG_* bits, or None)."""
+
+    def __init__(self, completeness, summary, num_brokers, brokers, diagnostics):
+        self.completeness, self.summary, self.num_brokers = completeness, summary, num_brokers
+        self.brokers, self.diagnostics = brokers, diagnostics
+
+
+class SlowBrokerFinder:
+    """SlowBrokerFinder with its slowness scores on the device (ccmi_slow_broker_finder_*), bound to one broker
+    MetricSampleAggregator, which it keeps alive. The keyword defaults are the reference's.
+
+        finder = SlowBrokerFinder(agg, log_flush_metric, leader_bytes_in_metric, replication_bytes_in_metric)
+        d = finder.detect(now_ms)          # one metricAnomalies round at time now_ms
+        d.brokers, d.summary.unfixable, finder.scores()
+    """
+
+    def __init__(self, aggregator: MetricSampleAggregator, log_flush_metric: int, leader_bytes_in_metric: int,
+                 replication_bytes_in_metric: int, bytes_in_rate_detection_threshold: float = 1024.0,
+                 log_flush_time_threshold_ms: float = 1000.0, metric_history_percentile: float = 90.0,
+                 metric_history_margin: float = 3.0, peer_metric_percentile: float = 50.0,
+                 peer_metric_margin: float = 3.0, demotion_score: int = 5, decommission_score: int = 50,
+                 self_healing_unfixable_ratio: float = 0.1, removal_enabled: bool = False):
+        self.aggregator, self.lib = aggregator, aggregator.lib
+        self.handle = None
+        if not self.lib.has_metric_anomalies:
+            raise UnsupportedOperationException(f"{self.lib.path} does not export ccmi_slow_broker_finder_create: "
+                                                "the anomaly finders run on the device only")
+        cfg = SlowBrokerConfigStruct(float(bytes_in_rate_detection_threshold), float(log_flush_time_threshold_ms),
+                                     float(metric_history_percentile), float(metric_history_margin),
+                                     float(peer_metric_percentile), float(peer_metric_margin),
+                                     float(self_healing_unfixable_ratio), int(demotion_score), int(decommission_score),
+                                     int(log_flush_metric), int(leader_bytes_in_metric),
+                                     int(replication_bytes_in_metric), 1 if removal_enabled else 0)
+        h = C.c_void_p()
+        self.lib.check(self.lib.lib.ccmi_slow_broker_finder_create(aggregator.handle, C.byref(cfg), C.byref(h)))
+        self.handle = h
+
+    def __del__(self):
+        try:
+            if self.handle:
+                self.lib.lib.ccmi_slow_broker_finder_destroy(self.handle)
+        except Exception:
+            pass
+
+    def detect(self, time_ms: int, to_ms: Optional[int] = None, from_ms: int = -1,
+               options: Optional[AggregationOptions] = None, interested=None, capacity: Optional[int] = None,
+               diagnostics: bool = False) -> SlowBrokerDetection:
+        """SlowBrokerFinder.metricAnomalies at _kafkaCruiseControl.timeMs() == time_ms; the history range ends at
+        to_ms (by default time_ms). Every call is one round of the score update."""
+        import numpy as np
+
+        agg = self.aggregator
+        s, arrays = agg._completeness_struct(np)
+        mask = agg._mask(np, interested)
+        cap = agg.E if capacity is None else int(capacity)
+        rec = np.zeros(max(cap, 0), dtype=SLOW_BROKER_DTYPE)
+        diag = np.zeros(agg.E, dtype=np.uint8) if diagnostics else None
+        o = (options or AggregationOptions(0.0, 0.0, 1, 5, GRANULARITY_ENTITY, False)).struct()
+        summary = SlowBrokerSummaryStruct()
+        n = C.c_int64(0)
+        self.lib.check(self.lib.lib.ccmi_slow_broker_finder_detect(
+            self.handle, from_ms, time_ms if to_ms is None else to_ms, C.byref(o),
+            mask.ctypes.data if mask is not None else None, time_ms, C.byref(s), C.byref(summary),
+            rec.ctypes.data if cap else None, cap, C.byref(n), diag.ctypes.data if diagnostics else None))
+        return SlowBrokerDetection(AggregatorCompleteness(np, s, arrays), summary, int(n.value),
+                                   rec[:max(0, min(cap, n.value))], diag)
+
+    def scores(self, capacity: Optional[int] = None):
+        """-> numpy records (entity, kind 0, score, since_ms) of the scored entities, ascending."""
+        import numpy as np
+
+        cap = self.aggregator.E if capacity is None else int(capacity)
+        rec = np.zeros(max(cap, 0), dtype=SLOW_BROKER_DTYPE)
+        n = C.c_int64(0)
+        self.lib.check(self.lib.lib.ccmi_slow_broker_finder_scores(self.handle, rec.ctypes.data if cap else None, cap,
+                                                                   C.byref(n)))
+        return rec[:max(0, min(cap, n.value))]
+
+    def reset(self) -> None:
+        self.lib.check(self.lib.lib.ccmi_slow_broker_finder_reset(self.handle))
 
 
 class ClusterModel:

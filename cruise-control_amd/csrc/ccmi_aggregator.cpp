@@ -181,7 +181,7 @@ int64_t runRows(ccmi_aggregator& a, int source, const std::vector<long long>& wi
 namespace ccmi {
 
 AggDeviceRows aggRowsOnDevice(ccmi_aggregator& a, int source, const std::vector<long long>& windows,
-                              int maxExtrapolations, int64_t capacity, bool wantInvalid) {
+                              int maxExtrapolations, int64_t capacity, bool wantInvalid, DBuf* target) {
   const int E = a.cfg.num_entities, M = a.cfg.num_metrics, Wv = (int)windows.size();
   const int tiles = (E + ccmi::kAggTile - 1) / ccmi::kAggTile;
   char* sm = (char*)a.small.ensure(align256((size_t)E) + 4096 + align256(sizeof(uint32_t) * ((size_t)tiles + 1)) +
@@ -199,7 +199,7 @@ AggDeviceRows aggRowsOnDevice(ccmi_aggregator& a, int source, const std::vector<
   d.k = k;
   const size_t bEnt = align256(sizeof(int32_t) * (size_t)k), bVal = align256(sizeof(float) * (size_t)k * M * Wv),
                bEx = align256((size_t)k * Wv), bInv = align256((size_t)k);
-  char* rb = (char*)a.rows.ensure(bEnt + bVal + bEx + bInv);
+  char* rb = (char*)(target ? *target : a.rows).ensure(bEnt + bVal + bEx + bInv);
   d.entities = (int32_t*)rb;
   d.values = (float*)(rb + bEnt);
   d.extrapolations = (uint8_t*)(rb + bEnt + bVal);

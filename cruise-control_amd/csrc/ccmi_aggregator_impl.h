@@ -68,6 +68,7 @@ struct ccmi_aggregator {
   ccmi::HBuf pinUp, pinDown;   // K18: pinned staging of the topology going up and of the columns coming down
   ccmi::DBuf loadIn, loadOut;  // K18 (ccmi_load_model.cpp): the uploaded topology and per-row scratch, the builder columns
   double loadTiming[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the last bulk load's split (ccmi_load_model_timing)
+  ccmi::DBuf rowsCurrent, anom, anomOut;  // K19 (ccmi_anomaly.cpp): the current rows beside a.rows, the scratch, the records
 
   ~ccmi_aggregator() {
     if (st) (void)hipStreamDestroy(st);
@@ -93,7 +94,7 @@ struct WalkResult {
   std::vector<long long> validWindows;  // newest first
 };
 
-// The rows of an aggregate as agg_rows left them in a.rows (valid until the aggregator's next call).
+// The rows of an aggregate as agg_rows left them in a.rows or the caller's buffer (valid until the aggregator's next call).
 struct AggDeviceRows {
   int64_t covered = 0, k = 0;  // the covered entities and how many of them have a row: min(capacity, covered)
   int32_t* entities = nullptr;
@@ -107,8 +108,9 @@ void aggCheckOptions(const ccmi_aggregation_options* o);
 bool aggPrepareAggregate(ccmi_aggregator& a, int64_t fromMs, int64_t toMs, const ccmi_aggregation_options& o,
                          const uint8_t* interested, ccmi_aggregator_completeness* out, WalkResult* walk);
 // Compacts the covered entities (source: 0 interested, 1 valid, 2 present) and writes the rows below `capacity` into
-// a.rows. Synchronises once (the covered count); the rows kernel is only enqueued.
+// a.rows, or into `target` when one is given (K19 keeps two row sets alive). Synchronises once (the covered count); the
+// rows kernel is only enqueued.
 AggDeviceRows aggRowsOnDevice(ccmi_aggregator& a, int source, const std::vector<long long>& windows,
-                              int maxExtrapolations, int64_t capacity, bool wantInvalid);
+                              int maxExtrapolations, int64_t capacity, bool wantInvalid, DBuf* target = nullptr);
 
 }  // namespace ccmi

@@ -84,4 +84,68 @@ void loadLaunchColumns(const LoadTopology& T, const LoadRows& R, const LoadScrat
 // C.load through engine/replica_load.h, tiles of whole replicas staged in LDS; numReplicas = state[kLoadStateReplicas]
 void loadLaunchLoads(const LoadRows& R, const LoadColumns& C, long long numReplicas, hipStream_t st);
 
+// ---- K19 (kernels/anomaly.hip): the metric anomaly finders over two row sets aggLaunchRows left on the device, as
+// ccmi_aggregator_metric_anomalies and ccmi_slow_broker_finder_detect (ccmi_anomaly.cpp) call them. All pointers are
+// device memory; the percentile is engine/percentile.h.
+struct AnomRows {  // entities ascending, values [k][M][W] (W = 1 for the current rows); k = 0 leaves the pointers unread
+  const int32_t* entities;
+  const float* values;
+  long long k;
+  int32_t M, W;
+};
+struct AnomRecord {  // ccmi_metric_anomaly
+  int32_t entity, metric;
+  double current, upper, lower;
+};
+struct AnomPercentile {  // ccmi_metric_anomaly_config
+  double upper, lower, upperMargin, lowerMargin;
+};
+struct AnomSlow {  // ccmi_slow_broker_config as the kernels take it
+  double bytesThreshold, flushThreshold, historyPercentile, historyMargin, peerPercentile, peerMargin;
+  int32_t demotion, decommission, mFlush, mIn, mRepl;
+};
+struct AnomSlowRecord {  // ccmi_slow_broker
+  int32_t entity, kind, score, reserved;
+  long long since;
+};
+struct AnomSlowScratch {  // one round's per-row scratch over the k current rows
+  double* cur;              // [2][k] the current log flush time and per-byte log flush time
+  uint8_t* historyHit;      // [2][k]
+  uint8_t* skipped;         // [k]
+  SortEntry* sortA;         // [2][k] {lo = row, hi = ordered key of cur}; a skipped row and a NaN sort last
+  SortEntry* sortB;         // [2][k] the merge passes' other buffer
+  unsigned long long* offsets;  // [3] = {0, k, 2k}
+  double* base;             // [2] the peer bases (NaN when not evaluated)
+  unsigned long long* ctr;  // [kAnomCtrWords]
+};
+struct AnomScores {  // the finder's state
+  int32_t* score;    // [E]
+  long long* since;  // [E]
+  uint8_t* has;      // [E] a key of _brokerSlownessScore and of _detectedSlowBrokers
+};
+// rowOf[E] = the row of each entity in `rows`, -1 for none
+void anomLaunchRowOf(const AnomRows& rows, int32_t E, int32_t* rowOf, hipStream_t st);
+// The percentile finder: one lane per (current row, metric) writes flags[item] and staged[item]; flags is scanned in
+// place afterwards (flags[items] = the count).
+void anomLaunchPercentile(const AnomRows& history, const AnomRows& current, const int32_t* historyRowOf,
+                          const uint8_t* interestedMetrics, const AnomPercentile& p, uint32_t* flags, AnomRecord* staged,
+                          hipStream_t st);
+// out[rank] = staged[item] for the flagged items whose rank is below capacity
+void anomLaunchGather(const uint32_t* flags, const AnomRecord* staged, long long items, long long capacity,
+                      AnomRecord* out, hipStream_t st);
+// The slow broker finder's round up to the peer bases: per-row currents, filtered history hits, the sort of the active
+// currents and the two bases. S.ctr is cleared here.
+void anomLaunchSlowRows(const AnomRows& history, const AnomRows& current, const int32_t* historyRowOf,
+                        const AnomSlow& p, const AnomSlowScratch& S, hipStream_t st);
+// updateBrokerSlownessScore and createSlowBrokerAnomalies, one lane per entity: flags[e] = 1 for a reported broker
+// (scanned in place afterwards, flags[E] = the count), kind[e], diag[e], the counters.
+void anomLaunchSlowUpdate(const AnomRows& current, const int32_t* currentRowOf, int32_t E, const AnomSlow& p,
+                          const AnomSlowScratch& S, const AnomScores& scores, long long timeMs, uint32_t* flags,
+                          uint8_t* kind, uint8_t* diag, hipStream_t st);
+// flags[e] = has[e], scanned in place (flags[E] = the count); kind[e] = 0
+void anomLaunchScoreFlags(const AnomScores& scores, int32_t E, uint32_t* flags, uint8_t* kind, hipStream_t st);
+// out[rank] = {e, kind[e], score[e], since[e]} for the flagged entities whose rank is below capacity
+void anomLaunchSlowGather(const uint32_t* flags, const uint8_t* kind, const AnomScores& scores, int32_t E,
+                          long long capacity, AnomSlowRecord* out, hipStream_t st);
+
 }  // namespace ccmi

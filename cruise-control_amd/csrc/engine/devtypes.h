@@ -607,4 +607,15 @@ struct AggWalk {
   unsigned long long* ctr;
 };
 
+// The metric anomaly finders over an aggregator's rows (kernels/anomaly.hip, K19). One lane per (current row, slot):
+// a slot is a metric for the percentile finder, and the log flush time or the per-byte log flush time for the slow
+// broker finder. A workgroup stages its lanes' histories as doubles in LDS, kAnomMaxHistory per lane, lane-minor.
+constexpr int kAnomBlock = 128;       // 2 waves; 31 KB of LDS per workgroup
+constexpr int kAnomMaxBlocks = 1024;  // workgroups of a grid-stride pass
+constexpr int kAnomMaxHistory = 31;   // the aggregator keeps at most 31 windows besides the current one
+// counters of one slow broker round
+enum : int {
+  kAnActive = 0, kAnNaNFlush, kAnNaNPerByte, kAnSkipped, kAnScored, kAnDemote, kAnRemove, kAnPeerEvaluated, kAnomCtrWords
+};
+
 }  // namespace ccmi

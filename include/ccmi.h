@@ -46,6 +46,12 @@
  *                              <- MonitorUtils.populatePartitionLoad for every partition of an aggregate
  *                                 monitor/LoadMonitor.java:491-543, monitor/MonitorUtils.java:415-479 (one device call
  *                                 from the aggregator's rows to the model builder)
+ *   ccmi_aggregator_metric_anomalies
+ *                              <- PercentileMetricAnomalyFinder.metricAnomalies  cruise-control-core
+ *                                 detector/metricanomaly/PercentileMetricAnomalyFinder.java:64-93, :140-177
+ *   ccmi_slow_broker_finder_*  <- SlowBrokerFinder.metricAnomalies  detector/SlowBrokerFinder.java:163-422 (the two
+ *                                 finders MetricAnomalyDetector.run hands the broker aggregator's history and current
+ *                                 window to, detector/MetricAnomalyDetector.java:69-75; the rows stay on the device)
  *   ccmi_random_cluster        <- test fixture RandomCluster.generate+populate
  *                                 (src/test/java/.../model/RandomCluster.java:53-455)
  *
@@ -1110,6 +1116,132 @@ ccmi_status ccmi_builder_populate_from_aggregator(
     const int32_t metric_of[6] /* aggregator metric index of each ccmi_metric, e.g. {0,1,2,3,7,8} */,
     const ccmi_partition_topology* topology, ccmi_aggregator_completeness* out,
     int64_t* num_rows /* rows of the aggregate */, int64_t* num_populated /* partitions added to the builder */);
+
+/*
+ * ccmi_aggregator_metric_anomalies and ccmi_slow_broker_finder_*, additive at ABI v13: the capability flag is the
+ * presence of the symbols. The two MetricAnomalyFinders that MetricAnomalyDetector.run
+ * (detector/MetricAnomalyDetector.java:69-75) hands a broker aggregator's history and current window to, over an
+ * existing ccmi_aggregator whose entities are brokers, groups hosts (BrokerEntity.group()) and metrics the caller's
+ * broker metric ids. Both calls take (from_ms, to_ms, options, interested) as ccmi_aggregator_aggregate does and
+ * compute two row sets on the device (K19) that never come to the host:
+ *   history = the rows of that aggregate. KafkaBrokerMetricSampleAggregator.aggregate uses ratios 0.0 / 0.0,
+ *             min_valid_windows 1, granularity ENTITY, include_invalid_entities false, from -1, to now.
+ *             NotEnoughValidWindows, or no window in range, is the reference's empty map: out->failure is set, there
+ *             are no history rows, and the finder still runs.
+ *   current = the rows of peekCurrentWindow: every present entity, the aggregator's current window, no interest mask.
+ * An entity "has history" iff it is a row of the aggregate. History values are newest first, latest() is value 0 of
+ * the current row (a Java float: the one sum of two latest() values, the current bytes in rate of the slow broker
+ * finder, is a float sum widened afterwards); every other float is widened to double before any arithmetic
+ * (MetricValues.doubleArray, and the double variables latest() is assigned to). The percentile
+ * is commons-math3 3.6.1's Percentile with its defaults (LEGACY estimation, NaNStrategy.REMOVED), results bit for
+ * bit up to the sign of a zero; isDataSufficient is PercentileMetricAnomalyFinderUtils.java:28-35. `out` is filled
+ * as ccmi_aggregator_aggregate fills it. Neither call changes the aggregator. No exception of the reference is
+ * reachable on these inputs: the finders' null checks guard maps that always exist here, and a percentile of 0 or
+ * 100 (where Percentile.evaluate would throw for 0) makes isDataSufficient false before evaluate is reached.
+ *
+ * ccmi_aggregator_metric_anomalies: PercentileMetricAnomalyFinder.metricAnomalies (:140-177) with getAnomalyForMetric
+ * (:64-93). With no history row, or !isDataSufficient(Wv, upper, lower) for the aggregate's Wv valid windows, there is
+ * no anomaly. Otherwise, for every current entity that has history and every metric m with interested_metrics[m]:
+ * u = percentile(history, upper); u <= 1 (SIGNIFICANT_METRIC_VALUE_THRESHOLD) is no anomaly; else upper_threshold =
+ * u * (1 + upper_margin), lower_threshold = percentile(history, lower) * lower_margin, current = latest, an anomaly iff
+ * current > upper_threshold || current < lower_threshold. The records come in ascending (entity, metric) order.
+ * *num_anomalies is always the full count (numAnomaliesOfType(RECENT)); capacity 0 with anomalies NULL is the sizing
+ * call; records beyond min(capacity, count) are untouched. *current_window_index is the window of the current rows.
+ * The description string and the KafkaMetricAnomaly object stay with the caller: the record carries every number the
+ * string formats, `out` the history windows.
+ * Errors, CCMI_E_INVALID: a NULL argument that is not marked nullable, capacity < 0, malformed options, a percentile
+ * outside [0.01, 99.99], upper_margin outside [0, 10], lower_margin outside [0, 1] (the ConfigDef ranges).
+ *
+ * ccmi_slow_broker_finder: SlowBrokerFinder with its state, bound to one aggregator (which must outlive it); score[E]
+ * and since_ms[E] (_brokerSlownessScore, _detectedSlowBrokers) live on the device. One detect is one
+ * metricAnomalies (:340-353) at _kafkaCruiseControl.timeMs() == time_ms:
+ *   1. per current entity: bytes = latest(leader_bytes_in) + latest(replication_bytes_in); skipped iff bytes <
+ *      bytes_in_rate_detection_threshold; else flush = latest(log_flush), per_byte = flush / bytes, and with history
+ *      the flush history keeps the values > 5.0, the per-byte history flush[i] / (in[i] + repl[i]) where that sum >=
+ *      the threshold;
+ *   2. getMetricAnomalies for each of the two metrics, the union of: from history, for an entity with history and
+ *      isDataSufficient(kept, hp, hp), cur > percentile(kept, hp) * history margin; from peers, if
+ *      isDataSufficient(active, pp, pp), cur > percentile(all active current values, pp) * peer margin (also with
+ *      no history at all);
+ *   3. suspects = both sets and flush > log_flush_time_threshold_ms;
+ *   4. updateBrokerSlownessScore (:360-386) for every entity, current or not: a suspect gets since = time_ms if it had
+ *      none and score = (none ? 1 : min(score + 1, decommission)); a scored non-suspect gets --score and leaves both
+ *      maps at 0;
+ *   5. createSlowBrokerAnomalies (:388-422): a suspect with score == decommission is "remove", else with score >=
+ *      demotion "demote"; PERSISTENT = removes, RECENT = demotes, SUSPECT = |since map| - both; unfixable iff
+ *      demotes + removes > cluster_size * unfixable ratio with cluster_size = the history rows.
+ * The reported brokers (kind 1 demote, 2 remove, in ascending entity order) follow the capacity convention above; every
+ * call is one round of the score update whatever the capacity, and E rows always suffice. When `unfixable` is set the
+ * reference reports all of them in one unfixable anomaly, else the demotes as one fixable anomaly and the removes as
+ * one whose fixability is removal_enabled. `diagnostics`, when given, receives one byte per entity
+ * (CCMI_SLOW_DIAG_*; 0 for an entity that is not current). scores() returns the scored entities ascending (kind 0);
+ * reset() forgets them.
+ * Errors, CCMI_E_INVALID (the predicates of configure :434-477): a threshold < 0, a percentile outside [0, 100], a
+ * margin < 1, a score < 0, a ratio outside [0, 1], a metric index outside [0, M); a NULL argument, capacity < 0,
+ * malformed options. On any error the finder's scores are unchanged. CCMI_E_DEVICE for a device failure.
+ */
+typedef struct ccmi_metric_anomaly_config {
+  double upper_percentile, lower_percentile;  /* metric.anomaly.percentile.{upper,lower}.threshold */
+  double upper_margin, lower_margin;          /* metric.anomaly.{upper,lower}.margin */
+} ccmi_metric_anomaly_config;
+typedef struct ccmi_metric_anomaly {
+  int32_t entity, metric;
+  double current, upper_threshold, lower_threshold;
+} ccmi_metric_anomaly;
+ccmi_status ccmi_aggregator_metric_anomalies(ccmi_aggregator* a, int64_t from_ms, int64_t to_ms,
+                                             const ccmi_aggregation_options* options,
+                                             const uint8_t* interested /* nullable [E] */,
+                                             const ccmi_metric_anomaly_config* config,
+                                             const uint8_t* interested_metrics /* [M] */,
+                                             ccmi_aggregator_completeness* out, int64_t* current_window_index,
+                                             ccmi_metric_anomaly* anomalies /* [capacity] */, int64_t capacity,
+                                             int64_t* num_anomalies);
+
+enum { CCMI_SLOW_BROKER_DEMOTE = 1, CCMI_SLOW_BROKER_REMOVE = 2 };
+enum {
+  CCMI_SLOW_DIAG_SKIPPED = 1,          /* negligible traffic */
+  CCMI_SLOW_DIAG_FLUSH_HISTORY = 2,    /* log flush time above its own history */
+  CCMI_SLOW_DIAG_FLUSH_PEERS = 4,      /* log flush time above its peers */
+  CCMI_SLOW_DIAG_PER_BYTE_HISTORY = 8, /* per-byte log flush time above its own history */
+  CCMI_SLOW_DIAG_PER_BYTE_PEERS = 16,  /* per-byte log flush time above its peers */
+  CCMI_SLOW_DIAG_OVER_THRESHOLD = 32,  /* log flush time above log_flush_time_threshold_ms */
+  CCMI_SLOW_DIAG_SUSPECT = 64
+};
+typedef struct ccmi_slow_broker_finder ccmi_slow_broker_finder;
+typedef struct ccmi_slow_broker_config {
+  double bytes_in_rate_detection_threshold, log_flush_time_threshold_ms;
+  double metric_history_percentile, metric_history_margin;
+  double peer_metric_percentile, peer_metric_margin;
+  double self_healing_unfixable_ratio;
+  int32_t demotion_score, decommission_score;
+  int32_t log_flush_metric, leader_bytes_in_metric, replication_bytes_in_metric; /* indices into the M metrics */
+  int32_t removal_enabled;
+} ccmi_slow_broker_config;
+typedef struct ccmi_slow_broker_summary {
+  int64_t current_window_index;
+  double peer_base_log_flush, peer_base_per_byte; /* NaN when not evaluated */
+  int32_t num_current, num_skipped, num_active;
+  int32_t cluster_size;                           /* history rows */
+  int32_t num_persistent, num_recent, num_suspect;
+  int32_t num_to_demote, num_to_remove;
+  int32_t unfixable, removal_enabled, reserved;
+} ccmi_slow_broker_summary;
+typedef struct ccmi_slow_broker {
+  int32_t entity, kind, score, reserved;
+  int64_t since_ms;
+} ccmi_slow_broker;
+ccmi_status ccmi_slow_broker_finder_create(ccmi_aggregator* a, const ccmi_slow_broker_config* config,
+                                           ccmi_slow_broker_finder** out);
+void ccmi_slow_broker_finder_destroy(ccmi_slow_broker_finder* f);
+ccmi_status ccmi_slow_broker_finder_detect(ccmi_slow_broker_finder* f, int64_t from_ms, int64_t to_ms,
+                                           const ccmi_aggregation_options* options,
+                                           const uint8_t* interested /* nullable [E] */, int64_t time_ms,
+                                           ccmi_aggregator_completeness* out, ccmi_slow_broker_summary* summary,
+                                           ccmi_slow_broker* brokers /* [capacity] */, int64_t capacity,
+                                           int64_t* num_brokers, uint8_t* diagnostics /* nullable [E] */);
+ccmi_status ccmi_slow_broker_finder_scores(ccmi_slow_broker_finder* f, ccmi_slow_broker* scored /* [capacity] */,
+                                           int64_t capacity, int64_t* num_scored);
+ccmi_status ccmi_slow_broker_finder_reset(ccmi_slow_broker_finder* f);
 
 /*
  * Destination-sharded mode (one process per GPU): every rank creates a session on its own device from the same

@@ -1,0 +1,108 @@
+"""ccmi_aggregator_metric_anomalies and ccmi_slow_broker_finder_* in the header, the binding and on a library without
+them.
+
+The entry points are additive at ABI v13 and their capability flag is the presence of the symbols. The finders run on
+the device only, so the CPU tests' emulation build (tests/emu) does not export them: the binding loads all the same and
+both calls refuse with UnsupportedOperationException instead of answering on the host.
+"""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import ccmi
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SYMBOLS = ("ccmi_aggregator_metric_anomalies", "ccmi_slow_broker_finder_create", "ccmi_slow_broker_finder_destroy",
+           "ccmi_slow_broker_finder_detect", "ccmi_slow_broker_finder_scores", "ccmi_slow_broker_finder_reset")
+STRUCTS = (("ccmi_metric_anomaly_config", "MetricAnomalyConfigStruct", 32),
+           ("ccmi_metric_anomaly", "MetricAnomalyStruct", 32),
+           ("ccmi_slow_broker_config", "SlowBrokerConfigStruct", 80),
+           ("ccmi_slow_broker_summary", "SlowBrokerSummaryStruct", 72),
+           ("ccmi_slow_broker", "SlowBrokerStruct", 24))
+CTYPES = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
+
+
+def _read(*path):
+    return open(os.path.join(REPO, *path)).read()
+
+
+def test_symbols_are_additive_at_abi_13():
+    header = _read("include", "ccmi.h")
+    assert int(re.search(r"#define CCMI_ABI_VERSION (\d+)", header).group(1)) == 13 == ccmi.ABI_VERSION
+    assert ccmi.ANOMALY_SYMBOLS == SYMBOLS
+    for name in SYMBOLS:
+        assert name in ccmi.EXPORTED_SYMBOLS, name
+        assert re.search(r"^(ccmi_status|void) %s\(ccmi_(aggregator|slow_broker_finder)\* " % name, header, re.M), name
+    assert "typedef struct ccmi_slow_broker_finder ccmi_slow_broker_finder;" in header
+    # the list at the top and the contract
+    assert re.search(r"ccmi_aggregator_metric_anomalies\s+\*\s+<- PercentileMetricAnomalyFinder\.metricAnomalies", header)
+    assert re.search(r"ccmi_slow_broker_finder_\*\s+<- SlowBrokerFinder\.metricAnomalies", header)
+    flat = re.sub(r"\s*\n \*\s*", " ", header)  # the comment blocks as running text
+    assert "No exception of the reference is reachable on these inputs" in flat
+    assert "LEGACY estimation, NaNStrategy.REMOVED" in flat
+    # the enums the binding mirrors
+    assert re.search(r"CCMI_SLOW_BROKER_DEMOTE = 1, CCMI_SLOW_BROKER_REMOVE = 2", header)
+    assert (ccmi.SLOW_BROKER_DEMOTE, ccmi.SLOW_BROKER_REMOVE) == (1, 2)
+    for name in ("SKIPPED", "FLUSH_HISTORY", "FLUSH_PEERS", "PER_BYTE_HISTORY", "PER_BYTE_PEERS", "OVER_THRESHOLD",
+                 "SUSPECT"):
+        assert re.search(r"CCMI_SLOW_DIAG_%s = %d\b" % (name, getattr(ccmi, "SLOW_DIAG_" + name)), header), name
+    # no existing struct changed, no new perf counters
+    assert C.sizeof(ccmi.AggregatorCompletenessStruct) == 96 and C.sizeof(ccmi.AggregationOptionsStruct) == 32
+    assert [f for f, _ in ccmi.PerfStruct._fields_][-3:] == ["accept_launches", "accept_cells", "accept_kernel_ms"]
+
+
+def test_struct_mirrors_match_the_header():
+    header = _read("include", "ccmi.h")
+    for name, mirror, size in STRUCTS:
+        struct = getattr(ccmi, mirror)
+        assert C.sizeof(struct) == size, name
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), header, re.S).group(1)
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        declared = []
+        for decl in body.split(";"):
+            words = decl.split()
+            if words:
+                ctype = CTYPES[words[0]]
+                for field in "".join(words[1:]).split(","):
+                    declared.append((field, ctype))
+        assert declared == list(struct._fields_), name
+    assert ccmi.METRIC_ANOMALY_DTYPE.itemsize == 32 and ccmi.SLOW_BROKER_DTYPE.itemsize == 24
+    assert ccmi.SLOW_BROKER_DTYPE.fields["since_ms"][1] == 16 and ccmi.METRIC_ANOMALY_DTYPE.fields["current"][1] == 8
+    source = _read("cruise-control_amd", "csrc", "ccmi_anomaly.cpp")
+    for name, _, size in STRUCTS:
+        assert re.search(r"sizeof\(%s\) == %d\b" % (name, size), source), name
+
+
+def test_sources_and_documents():
+    assert "csrc/ccmi_anomaly.cpp csrc/kernels/anomaly.hip" in _read("cruise-control_amd", "Makefile")
+    kernel = _read("cruise-control_amd", "csrc", "kernels", "anomaly.hip")
+    assert '#include "../engine/percentile.h"' in kernel and '#include "segments.h"' in kernel
+    assert '#include "percentile.h"' in _read("tests", "cpp", "test_percentile.cpp")
+    assert "DBuf* target" in _read("cruise-control_amd", "csrc", "ccmi_aggregator_impl.h")
+    for doc in ("README.md", "DESIGN.md", "INTEGRATION.md"):
+        text = _read(doc)
+        assert "ccmi_aggregator_metric_anomalies" in text and "ccmi_slow_broker_finder" in text, doc
+    design = _read("DESIGN.md")
+    assert "K19" in design and "anomaly.hip" in design and "percentile.h" in design and "K19 measured" in design
+    assert "MetricAnomalyDetector" in _read("INTEGRATION.md")
+    assert "anomaly_probe.py" in _read("README.md")
+
+
+def test_emu_loads_without_the_symbols(emu_lib):
+    assert emu_lib.lib.ccmi_abi_version() == 13
+    assert emu_lib.has_metric_anomalies is False
+    for name in SYMBOLS:
+        assert not hasattr(emu_lib.lib, name), name
+
+
+def test_emu_finders_are_unsupported(emu_lib):
+    # the emulation library cannot create an aggregator either: a bare object stands in for one
+    agg = object.__new__(ccmi.MetricSampleAggregator)
+    agg.lib, agg.handle, agg.E, agg.G, agg.M, agg.num_windows = emu_lib, None, 4, 2, 3, 5
+    with pytest.raises(ccmi.UnsupportedOperationException):
+        agg.metric_anomalies(1000, np.ones(3, dtype=np.uint8))
+    with pytest.raises(ccmi.UnsupportedOperationException):
+        ccmi.SlowBrokerFinder(agg, 0, 1, 2)
