@@ -26,7 +26,7 @@ static_assert(sizeof(ccmi_aggregator_config) == 32 && sizeof(ccmi_aggregator_sta
 namespace {
 
 using ccmi::AggDeviceRows;
-using ccmi::align256;
+using ccmi::Carver;
 using ccmi::hipCheck;
 using ccmi::WalkResult;
 
@@ -47,33 +47,18 @@ long long windowIndexOf(long long timeMs, long long windowMs) {
   return (long long)((unsigned long long)(timeMs / windowMs) + 1ull);
 }
 
-// carves `bytes` out of a block, 256-byte aligned
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base((char*)b) {}
-  template <class P>
-  void take(P*& p, size_t bytes) {
-    p = (P*)(base ? base + off : nullptr);
-    off += align256(bytes);
-  }
-};
-
-size_t layoutState(ccmi_aggregator& a, void* base, int32_t*& group, uint8_t*& fn) {
-  Carver c(base);
+void layoutState(ccmi_aggregator& a, Carver& c, int32_t*& group, uint8_t*& fn) {
   const size_t E = a.cfg.num_entities, M = a.cfg.num_metrics, L = a.L();
   c.take(a.T.counts, L * E);
-  c.take(a.T.values, sizeof(float) * L * M * E);
-  c.take(a.T.valid, sizeof(uint32_t) * E);
-  c.take(a.T.extrap, sizeof(uint32_t) * E);
+  c.take(a.T.values, L * M * E);
+  c.take(a.T.valid, E);
+  c.take(a.T.extrap, E);
   c.take(a.T.present, E);
-  c.take(group, sizeof(int32_t) * E);
+  c.take(group, E);
   c.take(fn, M);
-  return c.off;
 }
 
-size_t layoutWalk(ccmi_aggregator& a, void* base) {
-  Carver c(base);
+void layoutWalk(ccmi_aggregator& a, Carver& c) {
   const size_t E = a.cfg.num_entities, G = a.cfg.num_groups, L = a.L();
   c.take(a.W.inter, E);
   c.take(a.W.ginter, G);
@@ -81,11 +66,18 @@ size_t layoutWalk(ccmi_aggregator& a, void* base) {
   c.take(a.W.validG, G);
   c.take(a.W.vfw, E);
   c.take(a.W.gValidW, G);
-  c.take(a.W.extrapCnt, sizeof(int32_t) * E);
-  c.take(a.W.gValidCnt, sizeof(uint32_t) * L * G);
+  c.take(a.W.extrapCnt, E);
+  c.take(a.W.gValidCnt, L * G);
   c.take(a.W.gInvalid, L * G);
-  c.take(a.W.ctr, sizeof(unsigned long long) * (ccmi::kAggCtrHead + L * ccmi::kAggCtrPerWindow));
-  return c.off;
+  c.take(a.W.ctr, ccmi::kAggCtrHead + L * ccmi::kAggCtrPerWindow);
+}
+
+void layoutSmall(ccmi_aggregator& a, Carver& c) {
+  const size_t E = a.cfg.num_entities, L = a.L();
+  c.take(a.S.mask, E);
+  c.take(a.S.sums, 2);
+  c.take(a.S.tileOff, (E + ccmi::kAggTile - 1) / ccmi::kAggTile + 1);
+  c.take(a.S.windows, L);
 }
 
 void checkOptions(const ccmi_aggregation_options* o) {
@@ -125,11 +117,8 @@ WalkResult runCompleteness(ccmi_aggregator& a, int64_t fromMs, int64_t toMs, con
   bool any = false;
   if (interested)
     for (int e = 0; e < E && !any; ++e) any = interested[e] != 0;
-  uint8_t* dMask = nullptr;
-  if (any) {
-    dMask = (uint8_t*)a.small.ensure(align256((size_t)E) + 4096);
-    a.up(dMask, interested, (size_t)E);
-  }
+  uint8_t* dMask = any ? a.S.mask : nullptr;
+  if (any) a.up(dMask, interested, (size_t)E);
   ccmi::AggWalkOptions wo{o.min_valid_entity_ratio, o.min_valid_entity_group_ratio,
                           o.max_allowed_extrapolations_per_entity, o.granularity == CCMI_GRANULARITY_ENTITY_GROUP};
   ccmi::aggLaunchWalk(a.T, a.W, dMask, r.firstWindow, r.numWindows, wo, a.st);
@@ -181,14 +170,10 @@ int64_t runRows(ccmi_aggregator& a, int source, const std::vector<long long>& wi
 namespace ccmi {
 
 AggDeviceRows aggRowsOnDevice(ccmi_aggregator& a, int source, const std::vector<long long>& windows,
-                              int maxExtrapolations, int64_t capacity, bool wantInvalid, DBuf* target) {
-  const int E = a.cfg.num_entities, M = a.cfg.num_metrics, Wv = (int)windows.size();
-  const int tiles = (E + ccmi::kAggTile - 1) / ccmi::kAggTile;
-  char* sm = (char*)a.small.ensure(align256((size_t)E) + 4096 + align256(sizeof(uint32_t) * ((size_t)tiles + 1)) +
-                                   align256(sizeof(long long) * (size_t)std::max(Wv, 1)));
-  uint32_t* dTileOff = (uint32_t*)(sm + align256((size_t)E) + 4096);  // behind the interested mask of the walk
-  long long* dWindows = (long long*)((char*)dTileOff + align256(sizeof(uint32_t) * ((size_t)tiles + 1)));
-  ccmi::aggLaunchCover(a.T, a.W, source, dTileOff, a.st);
+                              int maxExtrapolations, int64_t capacity, bool wantInvalid, DevBuf* target) {
+  const int M = a.cfg.num_metrics, Wv = (int)windows.size();
+  if (Wv > a.L()) throw std::logic_error("more windows than the aggregator keeps");
+  ccmi::aggLaunchCover(a.T, a.W, source, a.S.tileOff, a.st);
   unsigned long long covered = 0;
   a.down(&covered, a.W.ctr + ccmi::kAcCovered, sizeof(covered));
   a.sync();
@@ -197,16 +182,15 @@ AggDeviceRows aggRowsOnDevice(ccmi_aggregator& a, int source, const std::vector<
   const int64_t k = std::min<int64_t>(capacity, (int64_t)covered);
   if (k <= 0) return d;
   d.k = k;
-  const size_t bEnt = align256(sizeof(int32_t) * (size_t)k), bVal = align256(sizeof(float) * (size_t)k * M * Wv),
-               bEx = align256((size_t)k * Wv), bInv = align256((size_t)k);
-  char* rb = (char*)(target ? *target : a.rows).ensure(bEnt + bVal + bEx + bInv);
-  d.entities = (int32_t*)rb;
-  d.values = (float*)(rb + bEnt);
-  d.extrapolations = (uint8_t*)(rb + bEnt + bVal);
-  d.invalid = (uint8_t*)(rb + bEnt + bVal + bEx);
-  a.up(dWindows, windows.data(), sizeof(long long) * (size_t)Wv);
-  ccmi::aggLaunchRows(a.T, a.W, source, dTileOff, dWindows, Wv, a.oldest, maxExtrapolations, k, d.entities, d.values,
-                      d.extrapolations, wantInvalid ? d.invalid : nullptr, a.st);
+  ccmi::carve(target ? *target : a.rows, [&](Carver& c) {
+    c.take(d.entities, (size_t)k);
+    c.take(d.values, (size_t)k * M * Wv);
+    c.take(d.extrapolations, (size_t)k * Wv);
+    c.take(d.invalid, (size_t)k);
+  });
+  a.up(a.S.windows, windows.data(), sizeof(long long) * (size_t)Wv);
+  ccmi::aggLaunchRows(a.T, a.W, source, a.S.tileOff, a.S.windows, Wv, a.oldest, maxExtrapolations, k, d.entities,
+                      d.values, d.extrapolations, wantInvalid ? d.invalid : nullptr, a.st);
   return d;
 }
 
@@ -268,10 +252,8 @@ extern "C" ccmi_status ccmi_aggregator_create(int32_t device_ordinal, const ccmi
     hipCheck(hipStreamCreateWithFlags(&a->st, hipStreamNonBlocking), "hipStreamCreate (aggregator)");
     int32_t* dGroup = nullptr;
     uint8_t* dFn = nullptr;
-    const size_t bytes = layoutState(*a, nullptr, dGroup, dFn);
-    void* base = a->state.ensure(bytes);
-    layoutState(*a, base, dGroup, dFn);
-    hipCheck(hipMemsetAsync(base, 0, bytes, a->st), "hipMemsetAsync (aggregator)");
+    const size_t bytes = ccmi::carve(a->state, [&](Carver& c) { layoutState(*a, c, dGroup, dFn); });
+    hipCheck(hipMemsetAsync(a->state.get(), 0, bytes, a->st), "hipMemsetAsync (aggregator)");
     a->up(dGroup, entity_group, sizeof(int32_t) * (size_t)config->num_entities);
     a->up(dFn, metric_function, (size_t)config->num_metrics);
     a->T.group = dGroup;
@@ -282,7 +264,8 @@ extern "C" ccmi_status ccmi_aggregator_create(int32_t device_ordinal, const ccmi
     a->T.L = a->L();
     a->T.minSamples = config->min_samples_per_window;
     a->T.halfMin = ccmi::agg::halfMinRequired(config->min_samples_per_window);
-    layoutWalk(*a, a->walk.ensure(layoutWalk(*a, nullptr)));
+    ccmi::carve(a->walk, [&](Carver& c) { layoutWalk(*a, c); });
+    ccmi::carve(a->small, [&](Carver& c) { layoutSmall(*a, c); });
     a->sync();
     *out = a.release();
     return CCMI_OK;
@@ -338,18 +321,22 @@ extern "C" ccmi_status ccmi_aggregator_add_samples(ccmi_aggregator* a, const int
     }
     const ccmi::DeviceGuard dg(a->device);
     const size_t E = (size_t)a->cfg.num_entities, M = (size_t)a->cfg.num_metrics, N = (size_t)n;
-    const size_t bEnt = align256(4 * N), bTime = align256(8 * N), bVal = align256(8 * N * M), bAcc = align256(N),
-                 bOrd = align256(4 * N), bRun = align256(4 * (E + 1)), bCur = align256(4 * E),
-                 bEv = align256(sizeof(ccmi::AggRollEvent) * std::max<size_t>(events.size(), 1));
-    char* b = (char*)a->batch.ensure(bEnt + bTime + bVal + bAcc + bOrd + bRun + bCur + bEv);
-    int32_t* dEnt = (int32_t*)b;
-    int64_t* dTime = (int64_t*)(b + bEnt);
-    double* dVal = (double*)(b + bEnt + bTime);
-    uint8_t* dAcc = (uint8_t*)(b + bEnt + bTime + bVal);
-    uint32_t* dOrd = (uint32_t*)(b + bEnt + bTime + bVal + bAcc);
-    uint32_t* dRun = (uint32_t*)(b + bEnt + bTime + bVal + bAcc + bOrd);
-    uint32_t* dCur = (uint32_t*)(b + bEnt + bTime + bVal + bAcc + bOrd + bRun);
-    ccmi::AggRollEvent* dEv = (ccmi::AggRollEvent*)(b + bEnt + bTime + bVal + bAcc + bOrd + bRun + bCur);
+    int32_t* dEnt;
+    int64_t* dTime;
+    double* dVal;
+    uint8_t* dAcc;
+    uint32_t *dOrd, *dRun, *dCur;
+    ccmi::AggRollEvent* dEv;
+    ccmi::carve(a->batch, [&](Carver& c) {
+      c.take(dEnt, N);
+      c.take(dTime, N);
+      c.take(dVal, N * M);
+      c.take(dAcc, N);
+      c.take(dOrd, N);
+      c.take(dRun, E + 1);
+      c.take(dCur, E);
+      c.take(dEv, events.size());
+    });
     a->up(dEnt, entity, 4 * N);
     a->up(dTime, time_ms, 8 * N);
     a->up(dVal, values, 8 * N * M);
@@ -372,10 +359,9 @@ extern "C" ccmi_status ccmi_aggregator_state_query(ccmi_aggregator* a, ccmi_aggr
   return guarded([&] {
     if (!a || !out) throw std::invalid_argument("null argument");
     const ccmi::DeviceGuard dg(a->device);
-    unsigned long long* d = (unsigned long long*)a->small.ensure(align256((size_t)a->cfg.num_entities) + 4096);
-    ccmi::aggLaunchStateSums(a->T, d, a->st);
+    ccmi::aggLaunchStateSums(a->T, a->S.sums, a->st);
     unsigned long long sums[2] = {0, 0};
-    a->down(sums, d, sizeof(sums));
+    a->down(sums, a->S.sums, sizeof(sums));
     a->sync();
     *out = ccmi_aggregator_state{};
     out->generation = a->generation;
@@ -446,9 +432,12 @@ extern "C" ccmi_status ccmi_aggregator_remove_entities(ccmi_aggregator* a, const
     for (int64_t i = 0; i < n; ++i)
       if (entities[i] < 0 || entities[i] >= a->cfg.num_entities) throw std::invalid_argument("entity id out of range");
     const ccmi::DeviceGuard dg(a->device);
-    char* b = (char*)a->batch.ensure(align256(4 * (size_t)n) + 256);
-    int32_t* dIds = (int32_t*)b;
-    uint32_t* dRemoved = (uint32_t*)(b + align256(4 * (size_t)n));
+    int32_t* dIds;
+    uint32_t* dRemoved;
+    ccmi::carve(a->batch, [&](Carver& c) {
+      c.take(dIds, (size_t)n);
+      c.take(dRemoved, 1);
+    });
     a->up(dIds, entities, 4 * (size_t)n);
     ccmi::aggLaunchRemove(a->T, dIds, n, dRemoved, a->st);
     uint32_t removed = 0;

@@ -1,6 +1,7 @@
-// What the two translation units behind ccmi_aggregator share (ccmi_aggregator.cpp, ccmi_load_model.cpp): the
-// aggregator object and the two steps of an aggregate that leave their result on the device. Private to the library;
-// include/ccmi.h only names the struct.
+// What the translation units behind ccmi_aggregator share (ccmi_aggregator.cpp, ccmi_load_model.cpp, ccmi_anomaly.cpp):
+// the aggregator object and the two steps of an aggregate that leave their result on the device. Its buffers are the
+// DevBuf / PinBuf of engine/devbuf.h, laid out with its Carver. Private to the library; include/ccmi.h only names the
+// struct.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,50 +10,18 @@
 
 #include "ccmi.h"
 #include "engine/aggregator.h"
+#include "engine/devbuf.h"
 #include "engine/hip_check.h"
 
 namespace ccmi {
 
-inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-// a device buffer that only grows
-struct DBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  void* ensure(size_t bytes) {
-    if (bytes > cap) {
-      if (p) (void)hipFree(p);
-      p = nullptr;
-      cap = 0;
-      const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-      ccmi::hipCheck(hipMalloc(&p, want), "hipMalloc (aggregator)");
-      cap = want;
-    }
-    return p;
-  }
-  ~DBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-// a pinned host buffer that only grows: the staging of K18's one copy in and one copy out
-struct HBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  void* ensure(size_t bytes) {
-    if (bytes > cap) {
-      if (p) (void)hipHostFree(p);
-      p = nullptr;
-      cap = 0;
-      const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-      ccmi::hipCheck(hipHostMalloc(&p, want, hipHostMallocDefault), "hipHostMalloc (aggregator)");
-      cap = want;
-    }
-    return p;
-  }
-  ~HBuf() {
-    if (p) (void)hipHostFree(p);
-  }
+// The pieces of ccmi_aggregator::small, every size fixed by the config (layoutSmall, ccmi_aggregator.cpp): what the
+// host hands a kernel beside the tables and the walk's scratch.
+struct AggSmall {
+  uint8_t* mask;             // [E] the interested mask of a walk
+  unsigned long long* sums;  // [2] ccmi_aggregator_state_query's sums
+  uint32_t* tileOff;         // [tiles + 1] the cover pass's tile offsets
+  long long* windows;        // [L] the window list of a rows pass: at most L windows can be valid
 };
 
 }  // namespace ccmi
@@ -64,11 +33,13 @@ struct ccmi_aggregator {
   ccmi::AggTables T{};
   ccmi::AggWalk W{};
   long long current = 0, oldest = 0, generation = 0;  // _currentWindowIndex, _oldestWindowIndex, _generation
-  ccmi::DBuf state, walk, batch, rows, small;
-  ccmi::HBuf pinUp, pinDown;   // K18: pinned staging of the topology going up and of the columns coming down
-  ccmi::DBuf loadIn, loadOut;  // K18 (ccmi_load_model.cpp): the uploaded topology and per-row scratch, the builder columns
+  ccmi::AggSmall S{};
+  ccmi::DevBuf state, walk, small;  // fixed by the config: allocated once, at create
+  ccmi::DevBuf batch, rows;         // grow with the batch and with the rows of an aggregate
+  ccmi::PinBuf pinUp, pinDown;  // K18: pinned staging of the topology going up and of the columns coming down
+  ccmi::DevBuf loadIn, loadOut;  // K18 (ccmi_load_model.cpp): the uploaded topology and per-row scratch, the builder columns
   double loadTiming[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the last bulk load's split (ccmi_load_model_timing)
-  ccmi::DBuf rowsCurrent, anom, anomOut;  // K19 (ccmi_anomaly.cpp): the current rows beside a.rows, the scratch, the records
+  ccmi::DevBuf rowsCurrent, anom, anomOut;  // K19 (ccmi_anomaly.cpp): the current rows beside a.rows, the scratch, the records
 
   ~ccmi_aggregator() {
     if (st) (void)hipStreamDestroy(st);
@@ -111,6 +82,6 @@ bool aggPrepareAggregate(ccmi_aggregator& a, int64_t fromMs, int64_t toMs, const
 // a.rows, or into `target` when one is given (K19 keeps two row sets alive). Synchronises once (the covered count); the
 // rows kernel is only enqueued.
 AggDeviceRows aggRowsOnDevice(ccmi_aggregator& a, int source, const std::vector<long long>& windows,
-                              int maxExtrapolations, int64_t capacity, bool wantInvalid, DBuf* target = nullptr);
+                              int maxExtrapolations, int64_t capacity, bool wantInvalid, DevBuf* target = nullptr);
 
 }  // namespace ccmi

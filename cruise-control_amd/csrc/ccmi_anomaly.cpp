@@ -32,27 +32,16 @@ static_assert(sizeof(ccmi::AnomRecord) == sizeof(ccmi_metric_anomaly) &&
 struct ccmi_slow_broker_finder {
   ccmi_aggregator* a = nullptr;
   ccmi_slow_broker_config cfg{};
-  ccmi::DBuf state;
+  ccmi::DevBuf state;
   ccmi::AnomScores scores{};
   size_t stateBytes = 0;
 };
 
 namespace {
 
-using ccmi::align256;
 using ccmi::AnomRows;
+using ccmi::Carver;
 using ccmi::hipCheck;
-
-struct Carver {  // carves `bytes` out of a block, 256-byte aligned
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base((char*)b) {}
-  template <class P>
-  void take(P*& p, size_t bytes) {
-    p = (P*)(base ? base + off : nullptr);
-    off += align256(bytes);
-  }
-};
 
 bool within(double v, double lo, double hi) { return v >= lo && v <= hi; }  // false for a NaN
 
@@ -96,13 +85,11 @@ void checkSlowConfig(const ccmi_slow_broker_config& c, int M) {
     if (m < 0 || m >= M) throw std::invalid_argument("metric index out of range");
 }
 
-size_t layoutScores(ccmi_slow_broker_finder& f, void* base) {
-  Carver c(base);
+void layoutScores(ccmi_slow_broker_finder& f, Carver& c) {
   const size_t E = (size_t)f.a->cfg.num_entities;
-  c.take(f.scores.since, sizeof(long long) * E);
-  c.take(f.scores.score, sizeof(int32_t) * E);
+  c.take(f.scores.since, E);
+  c.take(f.scores.score, E);
   c.take(f.scores.has, E);
-  return c.off;
 }
 
 // the flagged entities of flags[E + 1] (scanned) as records, the first `capacity` of them; -> the full count
@@ -156,15 +143,12 @@ extern "C" ccmi_status ccmi_aggregator_metric_anomalies(ccmi_aggregator* a, int6
     uint32_t* dFlags = nullptr;
     ccmi::AnomRecord* dStaged = nullptr;
     uint8_t* dMetrics = nullptr;
-    auto layout = [&](void* base) {
-      Carver c(base);
-      c.take(dRowOf, sizeof(int32_t) * E);
-      c.take(dFlags, sizeof(uint32_t) * ((size_t)items + 1));
-      c.take(dStaged, sizeof(ccmi::AnomRecord) * (size_t)items);
+    ccmi::carve(a->anom, [&](Carver& c) {
+      c.take(dRowOf, E);
+      c.take(dFlags, (size_t)items + 1);
+      c.take(dStaged, (size_t)items);
       c.take(dMetrics, M);
-      return c.off;
-    };
-    layout(a->anom.ensure(layout(nullptr)));
+    });
     a->up(dMetrics, interested_metrics, M);
     ccmi::anomLaunchRowOf(rows.history, (int32_t)E, dRowOf, a->st);
     const ccmi::AnomPercentile p{config->upper_percentile, config->lower_percentile, config->upper_margin,
@@ -197,10 +181,8 @@ extern "C" ccmi_status ccmi_slow_broker_finder_create(ccmi_aggregator* a, const 
     std::unique_ptr<ccmi_slow_broker_finder> f(new ccmi_slow_broker_finder);
     f->a = a;
     f->cfg = *config;
-    f->stateBytes = layoutScores(*f, nullptr);
-    void* base = f->state.ensure(f->stateBytes);
-    layoutScores(*f, base);
-    hipCheck(hipMemsetAsync(base, 0, f->stateBytes, a->st), "hipMemsetAsync (slow broker finder)");
+    f->stateBytes = ccmi::carve(f->state, [&](Carver& c) { layoutScores(*f, c); });
+    hipCheck(hipMemsetAsync(f->state.get(), 0, f->stateBytes, a->st), "hipMemsetAsync (slow broker finder)");
     a->sync();
     *out = f.release();
     return CCMI_OK;
@@ -236,24 +218,21 @@ extern "C" ccmi_status ccmi_slow_broker_finder_detect(ccmi_slow_broker_finder* f
     uint32_t* dFlags = nullptr;
     uint8_t *dKind = nullptr, *dDiag = nullptr;
     ccmi::AnomSlowScratch S{};
-    auto layout = [&](void* base) {
-      Carver c(base);
-      c.take(S.sortA, sizeof(ccmi::SortEntry) * 2 * k1);
-      c.take(S.sortB, sizeof(ccmi::SortEntry) * 2 * k1);
-      c.take(S.cur, sizeof(double) * 2 * k1);
-      c.take(S.offsets, sizeof(unsigned long long) * 3);
-      c.take(S.base, sizeof(double) * 2);
-      c.take(S.ctr, sizeof(unsigned long long) * ccmi::kAnomCtrWords);
-      c.take(dHistoryRowOf, sizeof(int32_t) * E);
-      c.take(dCurrentRowOf, sizeof(int32_t) * E);
-      c.take(dFlags, sizeof(uint32_t) * (E + 1));
+    ccmi::carve(a.anom, [&](Carver& c) {
+      c.take(S.sortA, 2 * k1);
+      c.take(S.sortB, 2 * k1);
+      c.take(S.cur, 2 * k1);
+      c.take(S.offsets, 3);
+      c.take(S.base, 2);
+      c.take(S.ctr, ccmi::kAnomCtrWords);
+      c.take(dHistoryRowOf, E);
+      c.take(dCurrentRowOf, E);
+      c.take(dFlags, E + 1);
       c.take(S.historyHit, 2 * k1);
       c.take(S.skipped, k1);
       c.take(dKind, E);
       c.take(dDiag, E);
-      return c.off;
-    };
-    layout(a.anom.ensure(layout(nullptr)));
+    });
     const unsigned long long offsets[3] = {0ull, (unsigned long long)k, 2ull * k};
     a.up(S.offsets, offsets, sizeof(offsets));
     const ccmi_slow_broker_config& c = f->cfg;
@@ -308,13 +287,10 @@ extern "C" ccmi_status ccmi_slow_broker_finder_scores(ccmi_slow_broker_finder* f
     const size_t E = (size_t)a.cfg.num_entities;
     uint32_t* dFlags = nullptr;
     uint8_t* dKind = nullptr;
-    auto layout = [&](void* base) {
-      Carver c(base);
-      c.take(dFlags, sizeof(uint32_t) * (E + 1));
+    ccmi::carve(a.anom, [&](Carver& c) {
+      c.take(dFlags, E + 1);
       c.take(dKind, E);
-      return c.off;
-    };
-    layout(a.anom.ensure(layout(nullptr)));
+    });
     ccmi::anomLaunchScoreFlags(f->scores, (int32_t)E, dFlags, dKind, a.st);
     hipCheck(hipGetLastError(), "slow broker scores launch");
     uint32_t count = 0;
@@ -330,7 +306,7 @@ extern "C" ccmi_status ccmi_slow_broker_finder_reset(ccmi_slow_broker_finder* f)
     if (!f) throw std::invalid_argument("null finder");
     ccmi_aggregator& a = *f->a;
     const ccmi::DeviceGuard dg(a.device);
-    hipCheck(hipMemsetAsync(f->state.p, 0, f->stateBytes, a.st), "hipMemsetAsync (slow broker finder)");
+    hipCheck(hipMemsetAsync(f->state.get(), 0, f->stateBytes, a.st), "hipMemsetAsync (slow broker finder)");
     a.sync();
     return CCMI_OK;
   });

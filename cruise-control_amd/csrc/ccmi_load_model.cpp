@@ -27,7 +27,7 @@ static_assert(CCMI_NUM_METRICS == ccmi::rload::kMetrics && CCMI_M_REPLICATION_BY
 
 namespace {
 
-using ccmi::align256;
+using ccmi::Carver;
 using ccmi::hipCheck;
 
 constexpr int kEvents = 7;
@@ -53,16 +53,6 @@ struct Events {
 double wallMs(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
-
-struct Carver {  // 256-byte aligned pieces of one block
-  char* base;
-  size_t off = 0;
-  template <class P>
-  void take(P*& p, size_t count) {
-    p = (P*)(base ? base + off : nullptr);
-    off += align256(sizeof(P) * count);
-  }
-};
 
 // Everything about the topology that needs no row: the shape against the aggregator, the index ranges, the offsets.
 void checkTopology(const ccmi_partition_topology& t, int E) {
@@ -165,8 +155,7 @@ extern "C" ccmi_status ccmi_builder_populate_from_aggregator(
     uint8_t* dOffline;
     ccmi::LoadScratch S{};
     size_t inputBytes = 0;
-    auto layoutIn = [&](void* base) {
-      Carver c{(char*)base};
+    ccmi::carve(a->loadIn, [&](Carver& c) {
       c.take(dTopic, P);
       c.take(dNumber, P);
       c.take(dOff, P + 1);
@@ -181,10 +170,8 @@ extern "C" ccmi_status ccmi_builder_populate_from_aggregator(
       c.take(S.rank, k);
       c.take(S.replicaBase, k);
       c.take(S.state, (size_t)ccmi::kLoadStateWords);
-      return c.off;
-    };
-    char* dIn = (char*)a->loadIn.ensure(layoutIn(nullptr));
-    layoutIn(dIn);
+    });
+    char* dIn = (char*)a->loadIn.get();
     // one copy in: the caller's arrays gathered into pinned memory in the device block's own layout
     char* hIn = (char*)a->pinUp.ensure(inputBytes);
     auto stage = [&](const void* device, const void* src, size_t bytes) {
@@ -227,8 +214,7 @@ extern "C" ccmi_status ccmi_builder_populate_from_aggregator(
 
     ccmi::LoadColumns C{};
     size_t outputBytes = 0;
-    auto layoutOut = [&](void* base) {
-      Carver c{(char*)base};
+    ccmi::carve(a->loadOut, [&](Carver& c) {
       c.take(C.pTopic, nP);
       c.take(C.pNumber, nP);
       c.take(C.pEnd, nP);
@@ -240,10 +226,8 @@ extern "C" ccmi_status ccmi_builder_populate_from_aggregator(
       c.take(C.load, nR * per);
       outputBytes = c.off;  // what comes back; the descriptors stay on the device
       c.take(C.rDesc, nR);
-      return c.off;
-    };
-    char* dOut = (char*)a->loadOut.ensure(layoutOut(nullptr));
-    layoutOut(dOut);
+    });
+    char* dOut = (char*)a->loadOut.get();
     C.basePartition = (int32_t)P0;
     C.baseReplica = (int32_t)R0;
     ev.record(kEvWrite, a->st);

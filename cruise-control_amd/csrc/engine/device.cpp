@@ -206,6 +206,20 @@ Device::Device(int ordinal, int B, int R, int P, int T, int maxGoalSlots)
   }
 }
 
+// devbuf.h: the product's allocation calls, for every DevBuf and PinBuf of the library
+void* deviceAlloc(size_t bytes) {
+  void* p = nullptr;
+  hipCheck(hipMalloc(&p, bytes), "hipMalloc (DevBuf)");
+  return p;
+}
+void deviceFree(void* p) noexcept { (void)hipFree(p); }
+void* pinnedAlloc(size_t bytes) {
+  void* p = nullptr;
+  hipCheck(hipHostMalloc(&p, bytes, hipHostMallocDefault), "hipHostMalloc (PinBuf)");
+  return p;
+}
+void pinnedFree(void* p) noexcept { (void)hipHostFree(p); }
+
 Device::~Device() {
   (void)hipSetDevice(ordinal_);
   try {
@@ -300,25 +314,8 @@ Device::~Device() {
   if (qdir_) (void)hipFree(qdir_);
   if (kqMem_) (void)hipFree(kqMem_);
   if (dServerT0_) (void)hipFree(dServerT0_);
-  if (dAccept_) (void)hipFree(dAccept_);
-  for (void* p : statsRowAllocs_)  // brokerStats (device_accept.cpp)
-    if (p) (void)hipFree(p);
-  if (dStatMembers_) (void)hipFree(dStatMembers_);
-  for (void* p : plAllocs_)  // partitionLoad (device_accept.cpp)
-    if (p) (void)hipFree(p);
-  if (dPlOut_) (void)hipFree(dPlOut_);
-  for (void* p : pdAllocs_)  // proposalDiff (device_accept.cpp)
-    if (p) (void)hipFree(p);
-  if (dPdOut_) (void)hipFree(dPdOut_);
-  for (void* p : srAllocs_)  // sortedReplicas (device_accept.cpp)
-    if (p) (void)hipFree(p);
-  if (dSrRecords_) (void)hipFree(dSrRecords_);
-  if (dSrScores_) (void)hipFree(dSrScores_);
-  for (void* p : epAllocs_)  // executionPlan (device_accept.cpp)
-    if (p) (void)hipFree(p);
-  for (void* p : {(void*)dEpBuf_[0], (void*)dEpBuf_[1], (void*)dEpTasks_, (void*)dEpInterOut_, (void*)dEpIntraOut_,
-                  (void*)dEpLeaderOut_})
-    if (p) (void)hipFree(p);
+  // the acceptance output and the K12-K16 blocks (device_accept.cpp) are DevBuf members: they free themselves after
+  // this body, with ordinal_ still current
   if (hStage_) (void)hipHostFree(hStage_);
   if (hResult_) (void)hipHostFree(hResult_);
   if (ev0_) (void)hipEventDestroy(EV0);

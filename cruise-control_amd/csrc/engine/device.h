@@ -16,6 +16,7 @@
 #include <memory>
 #include <vector>
 
+#include "devbuf.h"
 #include "devtypes.h"
 #include "intra.h"
 #include "keyed_table.h"
@@ -348,7 +349,7 @@ class Device {
   // from members[0, nMembers) ({replica, disk} of every Disk._replicas entry), uploaded only when memberVer differs from
   // the last call's (setDiskUtil brings the disks' utilization current beforehand). One stream sync, one D2H copy per
   // output array. Counts into perf.statsLaunches / statsKernelMs / statsBytes. Not in the test emulation.
-  bool statsStaticUploaded() const { return dStatMeta_ != nullptr; }
+  bool statsStaticUploaded() const { return bool(statStatic_); }
   void uploadStatsStatic(const BrokerStatic* meta, int H, const int32_t* hOff, const int32_t* hBrk, const int32_t* hIdx,
                          const int32_t* dBroker);
   int statsHosts() const { return statH_; }
@@ -361,10 +362,10 @@ class Device {
   // partition ascending), the first min(q.entries, selected) as records. uploadPartitionNumbers once per session
   // (TopicPartition.partition() of every partition). partitionLoad: the pending row updates and the pending chain
   // loads (lrows / srows, syncChainLoads) reach the tables first; topicSel[T], brokerSel[B], tieRank[P] may each be
-  // null; records has room for min(q.entries, P) rows. A hand-written LSD radix sort on the device; the sort buffers are
-  // allocated on first use. Two stream syncs (the counts, then the rows) and one D2H copy of the returned rows. Counts
+  // null; records has room for min(q.entries, P) rows. A hand-written LSD radix sort on the device; the workspace is
+  // one block allocated on first use. Two stream syncs (the counts, then the rows) and one D2H copy of the returned rows. Counts
   // into perf.statsLaunches / statsKernelMs / statsBytes. Not in the test emulation.
-  bool partitionNumbersUploaded() const { return dPlNumber_ != nullptr; }
+  bool partitionNumbersUploaded() const { return bool(plStatic_); }
   void uploadPartitionNumbers(const int32_t* pNumber);
   void partitionLoad(const PlQuery& q, const uint8_t* topicSel, const uint8_t* brokerSel, const int32_t* tieRank,
                      ccmi_partition_load_record* records, int64_t* numRecords, int64_t* numSelected);
@@ -378,7 +379,7 @@ class Device {
   // min(capacity, proposals) are written in ascending partition order; summary may be null. Two stream syncs at most
   // (the summary, then the rows when there are any). Counts into perf.statsLaunches / statsKernelMs / statsBytes. Not
   // in the test emulation.
-  bool initialPlacementUploaded() const { return dPdInitDist_ != nullptr; }
+  bool initialPlacementUploaded() const { return bool(pdStatic_); }
   void uploadInitialPlacement(const int32_t* initDist, const int32_t* initLeaders, const int32_t* initDisks,
                               const int32_t* initLeaderDisks);
   void proposalDiff(const int32_t* curDisks, ccmi_proposal_record* records, int64_t capacity, int64_t* numRecords,
@@ -391,7 +392,7 @@ class Device {
   // topicExcluded[T] and topicIncluded[T] may each be null; offsets[n + 1] and *numRecords = offsets[n] are always
   // written; records (and scores, when not null) only when offsets[n] <= capacity. One stream sync for the offsets, one
   // more for the rows. Counts into perf.statsLaunches / statsKernelMs / statsBytes. Not in the test emulation.
-  bool sortedStaticUploaded() const { return dSrStatic_ != nullptr; }
+  bool sortedStaticUploaded() const { return bool(srStatic_); }
   void uploadSortedStatic(const int32_t* rStatic);
   void sortedReplicas(const SrQuery& q, const int32_t* seg, int n, const uint8_t* topicExcluded,
                       const uint8_t* topicIncluded, int64_t* offsets, ccmi_swap_replica* records, double* scores,
@@ -530,14 +531,14 @@ class Device {
   bool serverChain(const DevProgram& prog, int mode, const int32_t* a0, int n0, const int32_t* a1, int n1,
                    const int32_t* a2, int n2, int n, int m, int maxAccepts);
   void streamWait(const char* what, double seconds);
-  // one chunk's acceptBatch verdicts [rows][nGoals], maskBatch words [sources][W] or swapGridBatch codes [sources][pitch]
-  int8_t* dAccept_ = nullptr;
-  size_t acceptCap_ = 0;
-  void ensureAccept(size_t bytes);
+  // one chunk's acceptBatch verdicts [rows][nGoals], maskBatch words [sources][W] or swapGridBatch codes [sources][pitch],
+  // grown to the largest chunk so far
+  DevBuf acceptOut_;
+  int8_t* dAccept() const { return (int8_t*)acceptOut_.get(); }
   // device_accept.cpp, its only user. PlainLaunch: the scope of a call that launches on the session stream with no
   // server resident. acceptChunk: one chunk of acceptBatch / maskBatch / swapGridBatch — fill(p) writes the req-byte
   // request behind the staged row updates, prep takes both to HBM, launch(stream) starts the kernel and its outBytes of
-  // dAccept_ come back to dst; one stream sync, one accept launch counted. timedLaunch / addKernelMs: the HIP-event
+  // acceptOut_ come back to dst; one stream sync, one accept launch counted. timedLaunch / addKernelMs: the HIP-event
   // pair around a call's kernels and, after the stream wait, their time (kernel timing on).
   struct PlainLaunch;
   template <class Fill, class Launch>
@@ -550,65 +551,76 @@ class Device {
   int maskChunkSources_ = 4096;    // sources per launch (CCMI_MASK_CHUNK_SOURCES, read at session create)
   std::vector<int8_t> swapHost_;      // one chunk's pitched codes on the host, before the pitch is removed
   int64_t swapChunkCells_ = 1 << 24;  // padded swap cells per launch (CCMI_SWAP_CHUNK_CELLS, read at session create)
-  // brokerStats: static tables, the output rows in HBM ([B] broker rows | [H] host rows, [D] disk rows) and the member
-  // list of the disks with the Model::diskMemberVer it was built at (0 = none)
-  BrokerStatic* dStatMeta_ = nullptr;
-  int32_t *dStatHOff_ = nullptr, *dStatHBrk_ = nullptr, *dStatHIdx_ = nullptr, *dStatDBroker_ = nullptr;
-  ccmi_basic_stats* dStatRows_ = nullptr;
-  ccmi_disk_stats* dStatDisks_ = nullptr;
-  DiskMember* dStatMembers_ = nullptr;
-  size_t statMembersCap_ = 0;
+  // K12-K16 (device_accept.cpp; devbuf.h, DESIGN.md "Query workspaces"): per query one DevBuf per lifetime (the static
+  // tables of its upload, the workspace of its first use, the outputs that grow) and a struct of typed pointers that one
+  // layout function fills. "Uploaded" and "first use done" are bool(buffer): a block is there whole or not at all.
+  // brokerStats. Static: the broker columns [B], the hosts' CSR [H + 1], [B], [H], the output rows [B] broker rows |
+  // [H] host rows and, on a model with disks, the disks' brokers and output rows [D]. The member list of the disks grows,
+  // with the Model::diskMemberVer it was built at (0 = none).
+  struct StatTables {
+    BrokerStatic* meta = nullptr;
+    int32_t *hOff = nullptr, *hBrk = nullptr, *hIdx = nullptr, *dBroker = nullptr;
+    ccmi_basic_stats* rows = nullptr;
+    ccmi_disk_stats* disks = nullptr;
+  } stat_;
+  void layoutStat(Carver& c);
+  DevBuf statStatic_, statMembersBuf_;
   int64_t statMembers_ = 0;
   uint64_t statMemberVer_ = 0;
   int statH_ = 0;
-  std::vector<void*> statsRowAllocs_;
-  // partitionLoad: the static partition numbers, the query's arrays, the ping-pong sort buffers [P] each, the
-  // [256 x tiles] digit counts, the query state and the output rows (grown to the largest request so far)
-  int32_t *dPlNumber_ = nullptr, *dPlRank_ = nullptr;
-  uint8_t *dPlTopicSel_ = nullptr, *dPlBrokerSel_ = nullptr;
-  PlEntry* dPlBuf_[2] = {nullptr, nullptr};
-  uint32_t* dPlCounts_ = nullptr;
-  PlState* dPlState_ = nullptr;
-  ccmi_partition_load_record* dPlOut_ = nullptr;
-  size_t plOutCap_ = 0;
-  std::vector<void*> plAllocs_;
-  // proposalDiff: the initial placement (static), the current disks of a call [R], the [tiles + 1] tile counts, the
-  // sums and the output rows (grown to the largest capacity so far)
-  int32_t *dPdInitDist_ = nullptr, *dPdInitLeaders_ = nullptr, *dPdInitDisks_ = nullptr, *dPdInitLeaderDisks_ = nullptr;
-  int32_t* dPdCurDisks_ = nullptr;
-  uint32_t* dPdCounts_ = nullptr;
-  PdSums* dPdSums_ = nullptr;
-  ccmi_proposal_record* dPdOut_ = nullptr;
-  size_t pdOutCap_ = 0;
-  std::vector<void*> pdAllocs_;
-  // sortedReplicas: the static tail ranks [R], the segment map, counts and cursors [B], {total, longest, offsets} [B + 3],
-  // the topic masks [T], the keys and segments [R], the entry buffers [R] (the second one once a segment is longer than
-  // a tile) and the output rows (grown to the largest total so far)
-  int32_t *dSrStatic_ = nullptr, *dSrSeg_ = nullptr, *dSrSegOf_ = nullptr;
-  uint32_t *dSrCounts_ = nullptr, *dSrCursor_ = nullptr;
-  unsigned long long* dSrState_ = nullptr;
-  uint8_t *dSrTopicExcl_ = nullptr, *dSrTopicIncl_ = nullptr;
-  uint64_t* dSrKeys_ = nullptr;
-  SortEntry* dSrBuf_[2] = {nullptr, nullptr};
-  ccmi_swap_replica* dSrRecords_ = nullptr;
-  double* dSrScores_ = nullptr;
-  size_t srOutCap_ = 0;
-  std::vector<void*> srAllocs_;
+  // partitionLoad. Static: the partition numbers [P]. First use: the query's arrays, the ping-pong sort buffers [P]
+  // each, the [256 x tiles] digit counts, the query state. The output rows grow to the largest request so far.
+  struct PlWork {
+    int32_t* rank = nullptr;
+    uint8_t *topicSel = nullptr, *brokerSel = nullptr;
+    PlEntry* buf[2] = {nullptr, nullptr};
+    uint32_t* counts = nullptr;
+    PlState* state = nullptr;
+  } pl_;
+  void layoutPl(Carver& c);
+  DevBuf plStatic_, plWork_, plOut_;
+  // proposalDiff. Static: the initial placement (the disks only on a model with disks). First use: the [tiles + 1] tile
+  // counts, the current disks of a call [R], the sums. The output rows grow to the largest capacity so far.
+  struct PdStatic {
+    int32_t *initDist = nullptr, *initLeaders = nullptr, *initDisks = nullptr, *initLeaderDisks = nullptr;
+  } pdInit_;
+  struct PdWork {
+    uint32_t* counts = nullptr;
+    int32_t* curDisks = nullptr;
+    PdSums* sums = nullptr;
+  } pd_;
+  void layoutPdStatic(Carver& c);
+  void layoutPd(Carver& c);
+  DevBuf pdStatic_, pdWork_, pdOut_;
+  // sortedReplicas. Static, the call's scratch with it: the tail ranks [R], the segment map, counts and cursors [B],
+  // {total, longest, offsets} [B + 3], the topic masks [T], the keys and segments [R], the entry buffer [R]. The merge
+  // passes' second entry buffer [R] comes once a segment is longer than a tile. The output records and scores grow
+  // together to the largest total so far.
+  struct SrWork {
+    int32_t *rStatic = nullptr, *seg = nullptr, *segOf = nullptr;
+    uint32_t *counts = nullptr, *cursor = nullptr;
+    unsigned long long* state = nullptr;
+    uint8_t *topicExcl = nullptr, *topicIncl = nullptr;
+    uint64_t* keys = nullptr;
+    SortEntry* buf = nullptr;
+  } sr_;
+  void layoutSr(Carver& c);
+  DevBuf srStatic_, srMerge_, srOut_;
   std::vector<unsigned long long> srHost_;
-  // executionPlan: the rows and execution ids [P], the call's rank [P], state [P] and current disks [R], the tile
-  // counts [2][tiles + 1], the broker counts and cursors [2 B], the sums, {total, longest, offsets} of both lists and the
-  // two one-segment offsets [2 (B + 3) + 4]; the entry buffers and the output arrays grow to the largest call so far
-  EpRow* dEpRows_ = nullptr;
-  int32_t *dEpIdOf_ = nullptr, *dEpRank_ = nullptr, *dEpCurDisks_ = nullptr, *dEpOrder_ = nullptr;
-  uint8_t* dEpPState_ = nullptr;
-  uint32_t *dEpTiles_ = nullptr, *dEpCounts_ = nullptr, *dEpCursors_ = nullptr;
-  EpSums* dEpSums_ = nullptr;
-  unsigned long long* dEpState_ = nullptr;
-  SortEntry* dEpBuf_[2] = {nullptr, nullptr};
-  ccmi_plan_task* dEpTasks_ = nullptr;
-  int32_t *dEpInterOut_ = nullptr, *dEpIntraOut_ = nullptr, *dEpLeaderOut_ = nullptr;
-  size_t epBufCap_ = 0, epTaskCap_ = 0, epInterCap_ = 0, epIntraCap_ = 0, epLeaderCap_ = 0;
-  std::vector<void*> epAllocs_;
+  // executionPlan. First use: the rows and execution ids [P], the call's rank [P], state [P] and current disks [R], the
+  // broker order [B], the tile counts [2][tiles + 1], the broker counts and cursors [2 B], {total, longest, offsets} of
+  // both lists and the two one-segment offsets [2 (B + 3) + 4], the sums. The two entry buffers grow together (a merge
+  // pass may come with any call); each output list grows on its own to the largest call so far.
+  struct EpWork {
+    EpRow* rows = nullptr;
+    int32_t *idOf = nullptr, *rank = nullptr, *curDisks = nullptr, *order = nullptr;
+    uint8_t* pstate = nullptr;
+    uint32_t *tiles = nullptr, *counts = nullptr, *cursors = nullptr;
+    unsigned long long* state = nullptr;
+    EpSums* sums = nullptr;
+  } ep_;
+  void layoutEp(Carver& c);
+  DevBuf epWork_, epEntries_, epTasks_, epInter_, epIntra_, epLeader_;
   std::vector<unsigned long long> epHost_;
   // the pending chain loads (lrows / srows) go to the device's Java loads and slot order outside a chain
   void syncChainLoads();

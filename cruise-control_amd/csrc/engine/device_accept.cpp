@@ -60,6 +60,12 @@ hipError_t launchExecutionPlanFill(const EpTables& T, const EpQuery& q, int tile
 
 namespace {
 constexpr double kAcceptWaitSeconds = 120.0;
+
+// one table of a static block: a synchronous copy of the host's n elements
+template <class P>
+void upload(P* d, const P* h, size_t n, const char* what) {
+  if (h && n) hipCheck(hipMemcpy(d, h, n * sizeof(P), hipMemcpyHostToDevice), what);
+}
 }  // namespace
 
 // The session's device current and the device-scan phase open for the call; plain launches on the session stream, so the
@@ -90,16 +96,6 @@ void Device::addKernelMs(double& total) {
   total += ms;
 }
 
-// the output buffer of one chunk, grown to the largest chunk so far
-void Device::ensureAccept(size_t bytes) {
-  if (bytes <= acceptCap_) return;
-  if (dAccept_) hipCheck(hipFree(dAccept_), "hipFree");
-  dAccept_ = nullptr;
-  acceptCap_ = 0;
-  hipCheck(hipMalloc((void**)&dAccept_, bytes), "hipMalloc acceptance");
-  acceptCap_ = bytes;
-}
-
 template <class Fill, class Launch>
 void Device::acceptChunk(size_t req, Fill fill, size_t outBytes, Launch launch, void* dst, const char* kernel,
                          const char* copy) {
@@ -108,9 +104,9 @@ void Device::acceptChunk(size_t req, Fill fill, size_t outBytes, Launch launch, 
   const Staged g = packUpdates(req);
   fill(hStage_ + g.end);
   launchPrepFor(g, req, false);
-  ensureAccept(outBytes);
+  acceptOut_.ensure(outBytes);
   timedLaunch([&] { hipCheck(launch(st), kernel); });
-  hipCheck(hipMemcpyAsync(dst, dAccept_, outBytes, hipMemcpyDeviceToHost, st), copy);
+  hipCheck(hipMemcpyAsync(dst, dAccept(), outBytes, hipMemcpyDeviceToHost, st), copy);
   streamWait(kernel, kAcceptWaitSeconds);
   perf.syncs++;
   perf.acceptLaunches++;  // acceptCells is the caller's count: it knows which rows are padding and which exits were early
@@ -130,7 +126,7 @@ void Device::acceptBatch(const DevProgram& prog, const AcceptRow* rows, int64_t 
     const size_t req = (size_t)n * sizeof(AcceptRow);
     acceptChunk(
         req, [&](char* p) { std::memcpy(p, rows + r0, req); }, (size_t)n * G,
-        [&](hipStream_t st) { return launchAcceptActions(tables(), prog, (const AcceptRow*)dReq_, n, dAccept_, st); },
+        [&](hipStream_t st) { return launchAcceptActions(tables(), prog, (const AcceptRow*)dReq_, n, dAccept(), st); },
         out + (size_t)r0 * G, "accept_actions", "D2H acceptance");
   }
 }
@@ -147,7 +143,7 @@ void Device::maskBatch(const DevProgram& prog, const SourceRow* rows, int64_t nS
     acceptChunk(
         req, [&](char* p) { std::memcpy(p, rows + s0, req); }, (size_t)n * W * sizeof(uint64_t),
         [&](hipStream_t st) {
-          return launchAcceptMask(tables(), prog, (const SourceRow*)dReq_, n, (unsigned long long*)dAccept_, st);
+          return launchAcceptMask(tables(), prog, (const SourceRow*)dReq_, n, (unsigned long long*)dAccept(), st);
         },
         out + (size_t)s0 * W, "accept_mask", "D2H masks");
   }
@@ -179,7 +175,7 @@ void Device::swapGridBatch(const DevProgram& prog, const SourceRow* rows, int64_
         },
         (size_t)n * pitch,
         [&](hipStream_t st) {
-          return launchAcceptSwaps(tables(), prog, (const SourceRow*)dReq_, n, (const int32_t*)(dReq_ + oCand), m, dAccept_,
+          return launchAcceptSwaps(tables(), prog, (const SourceRow*)dReq_, n, (const int32_t*)(dReq_ + oCand), m, dAccept(),
                                    st);
         },
         compact ? swapHost_.data() : dst, "accept_swaps", "D2H swap codes");
@@ -192,29 +188,35 @@ void Device::uploadStatsStatic(const BrokerStatic* meta, int H, const int32_t* h
                                const int32_t* hIdx, const int32_t* dBroker) {
   DeviceGuard cur(ordinal_);
   stopServer();
-  if (dStatMeta_) throw std::logic_error("uploadStatsStatic: once per session");
+  if (statStatic_) throw std::logic_error("uploadStatsStatic: once per session");
   if (H < 1 || H > B_) throw std::logic_error("uploadStatsStatic: host count");
-  auto put = [&](auto** d, const auto* h, size_t n, const char* what) {
-    hipCheck(hipMalloc((void**)d, std::max<size_t>(1, n) * sizeof(**d)), what);
-    statsRowAllocs_.push_back(*d);
-    if (h && n) hipCheck(hipMemcpy(*d, h, n * sizeof(**d), hipMemcpyHostToDevice), what);
-  };
-  put(&dStatHOff_, hOff, (size_t)H + 1, "upload stats host offsets");
-  put(&dStatHBrk_, hBrk, (size_t)B_, "upload stats host brokers");
-  put(&dStatHIdx_, hIdx, (size_t)H, "upload stats host indices");
-  put(&dStatRows_, (const ccmi_basic_stats*)nullptr, (size_t)B_ + (size_t)H, "hipMalloc stats rows");
-  if (D_ > 0) {
-    put(&dStatDBroker_, dBroker, (size_t)D_, "upload stats disk brokers");
-    put(&dStatDisks_, (const ccmi_disk_stats*)nullptr, (size_t)D_, "hipMalloc disk stats rows");
-  }
   statH_ = H;
-  put(&dStatMeta_, meta, (size_t)B_, "upload stats broker columns");  // last: statsStaticUploaded()
+  DevBuf block;  // becomes statStatic_ once every table is up: statsStaticUploaded()
+  carve(block, [&](Carver& c) { layoutStat(c); });
+  upload(stat_.hOff, hOff, (size_t)H + 1, "upload stats host offsets");
+  upload(stat_.hBrk, hBrk, (size_t)B_, "upload stats host brokers");
+  upload(stat_.hIdx, hIdx, (size_t)H, "upload stats host indices");
+  if (D_ > 0) upload(stat_.dBroker, dBroker, (size_t)D_, "upload stats disk brokers");
+  upload(stat_.meta, meta, (size_t)B_, "upload stats broker columns");
+  statStatic_ = std::move(block);
+}
+
+void Device::layoutStat(Carver& c) {
+  c.take(stat_.hOff, (size_t)statH_ + 1);
+  c.take(stat_.hBrk, (size_t)B_);
+  c.take(stat_.hIdx, (size_t)statH_);
+  c.take(stat_.rows, (size_t)B_ + (size_t)statH_);
+  if (D_ > 0) {
+    c.take(stat_.dBroker, (size_t)D_);
+    c.take(stat_.disks, (size_t)D_);
+  }
+  c.take(stat_.meta, (size_t)B_);
 }
 
 void Device::brokerStats(ccmi_basic_stats* brokers, ccmi_basic_stats* hosts, ccmi_disk_stats* disks,
                          const DiskMember* members, int64_t nMembers, uint64_t memberVer) {
   PlainLaunch call(*this);
-  if (!dStatMeta_) throw std::logic_error("brokerStats before uploadStatsStatic");
+  if (!statStatic_) throw std::logic_error("brokerStats before uploadStatsStatic");
   if (!brokers || nMembers < 0) throw std::logic_error("brokerStats: arguments");
   const bool withDisks = disks && D_ > 0;
   const hipStream_t st = (hipStream_t)st_;
@@ -224,42 +226,38 @@ void Device::brokerStats(ccmi_basic_stats* brokers, ccmi_basic_stats* hosts, ccm
     launchPrepFor(g, 0, false);
   }
   if (withDisks && memberVer != statMemberVer_) {
-    if ((size_t)nMembers > statMembersCap_) {
-      if (dStatMembers_) hipCheck(hipFree(dStatMembers_), "hipFree");
-      dStatMembers_ = nullptr;
-      statMembersCap_ = 0;
-      hipCheck(hipMalloc((void**)&dStatMembers_, (size_t)nMembers * sizeof(DiskMember)), "hipMalloc disk members");
-      statMembersCap_ = (size_t)nMembers;
-    }
+    DiskMember* dMembers = (DiskMember*)statMembersBuf_.ensure((size_t)nMembers * sizeof(DiskMember));
     if (nMembers)
-      hipCheck(hipMemcpyAsync(dStatMembers_, members, (size_t)nMembers * sizeof(DiskMember), hipMemcpyHostToDevice, st),
+      hipCheck(hipMemcpyAsync(dMembers, members, (size_t)nMembers * sizeof(DiskMember), hipMemcpyHostToDevice, st),
                "upload disk members");
     statMembers_ = nMembers;
     statMemberVer_ = memberVer;
   }
-  ccmi_basic_stats* dHosts = dStatRows_ + B_;
+  ccmi_basic_stats* dHosts = stat_.rows + B_;
   int launches = 1;
   timedLaunch([&] {
-    hipCheck(launchBrokerStatsRows(brokers_, dStatMeta_, B_, dStatRows_, withDisks ? D_ : 0, dDUtilIn_, dDCap_,
-                                   dStatDBroker_, dStatDisks_, st),
+    hipCheck(launchBrokerStatsRows(brokers_, stat_.meta, B_, stat_.rows, withDisks ? D_ : 0, dDUtilIn_, dDCap_,
+                                   stat_.dBroker, stat_.disks, st),
              "broker_stats_rows");
     if (hosts) {
-      hipCheck(launchBrokerStatsHosts(dStatRows_, dStatHOff_, dStatHBrk_, dStatHIdx_, statH_, B_, dHosts, st),
+      hipCheck(launchBrokerStatsHosts(stat_.rows, stat_.hOff, stat_.hBrk, stat_.hIdx, statH_, B_, dHosts, st),
                "broker_stats_hosts");
       launches++;
     }
     if (withDisks && statMembers_ > 0) {
-      hipCheck(launchBrokerStatsDisks(dStatMembers_, statMembers_, replicas_, R_, D_, dStatDisks_, st), "broker_stats_disks");
+      hipCheck(launchBrokerStatsDisks((const DiskMember*)statMembersBuf_.get(), statMembers_, replicas_, R_, D_,
+                                      stat_.disks, st),
+               "broker_stats_disks");
       launches++;
     }
   });
-  hipCheck(hipMemcpyAsync(brokers, dStatRows_, (size_t)B_ * sizeof(ccmi_basic_stats), hipMemcpyDeviceToHost, st),
+  hipCheck(hipMemcpyAsync(brokers, stat_.rows, (size_t)B_ * sizeof(ccmi_basic_stats), hipMemcpyDeviceToHost, st),
            "D2H broker stats");
   if (hosts)
     hipCheck(hipMemcpyAsync(hosts, dHosts, (size_t)statH_ * sizeof(ccmi_basic_stats), hipMemcpyDeviceToHost, st),
              "D2H host stats");
   if (withDisks)
-    hipCheck(hipMemcpyAsync(disks, dStatDisks_, (size_t)D_ * sizeof(ccmi_disk_stats), hipMemcpyDeviceToHost, st),
+    hipCheck(hipMemcpyAsync(disks, stat_.disks, (size_t)D_ * sizeof(ccmi_disk_stats), hipMemcpyDeviceToHost, st),
              "D2H disk stats");
   streamWait("broker_stats", kAcceptWaitSeconds);
   perf.syncs++;
@@ -275,13 +273,21 @@ void Device::brokerStats(ccmi_basic_stats* brokers, ccmi_basic_stats* hosts, ccm
 void Device::uploadPartitionNumbers(const int32_t* pNumber) {
   DeviceGuard cur(ordinal_);
   stopServer();
-  if (dPlNumber_) throw std::logic_error("uploadPartitionNumbers: once per session");
+  if (plStatic_) throw std::logic_error("uploadPartitionNumbers: once per session");
   if (P_ < 1 || !pNumber) throw std::logic_error("uploadPartitionNumbers: arguments");
-  int32_t* d = nullptr;
-  hipCheck(hipMalloc((void**)&d, (size_t)P_ * sizeof(int32_t)), "hipMalloc partition numbers");
-  plAllocs_.push_back(d);
-  hipCheck(hipMemcpy(d, pNumber, (size_t)P_ * sizeof(int32_t), hipMemcpyHostToDevice), "upload partition numbers");
-  dPlNumber_ = d;
+  DevBuf block;  // the one table [P]
+  upload((int32_t*)block.ensure((size_t)P_ * sizeof(int32_t)), pNumber, (size_t)P_, "upload partition numbers");
+  plStatic_ = std::move(block);
+}
+
+void Device::layoutPl(Carver& c) {
+  c.take(pl_.rank, (size_t)P_);
+  c.take(pl_.topicSel, (size_t)T_);
+  c.take(pl_.brokerSel, (size_t)B_);
+  c.take(pl_.buf[0], (size_t)P_);
+  c.take(pl_.buf[1], (size_t)P_);
+  c.take(pl_.counts, (size_t)256 * (size_t)((P_ + kPlSortTile - 1) / kPlSortTile));
+  c.take(pl_.state, 1);
 }
 
 // What stageChainCopy does in front of a chain, without a request: the load and slot rows behind the staged row
@@ -306,51 +312,35 @@ void Device::syncChainLoads() {
 void Device::partitionLoad(const PlQuery& q, const uint8_t* topicSel, const uint8_t* brokerSel, const int32_t* tieRank,
                            ccmi_partition_load_record* records, int64_t* numRecords, int64_t* numSelected) {
   PlainLaunch call(*this);
-  if (!dPlNumber_) throw std::logic_error("partitionLoad before uploadPartitionNumbers");
+  if (!plStatic_) throw std::logic_error("partitionLoad before uploadPartitionNumbers");
   if (!numRecords || q.entries < 0 || q.resource < 0 || q.resource > 3 || q.mode < 0 || q.mode > 2)
     throw std::logic_error("partitionLoad: arguments");
   const int cap = std::min(q.entries, P_);
   if (cap > 0 && !records) throw std::logic_error("partitionLoad: no room for the records");
   const hipStream_t st = (hipStream_t)st_;
   const int tiles = (P_ + kPlSortTile - 1) / kPlSortTile;
-  if (!dPlState_) {  // first use: the query arrays, the sort buffers, the digit counts, the state
-    auto get = [&](auto** d, size_t n, const char* what) {
-      hipCheck(hipMalloc((void**)d, std::max<size_t>(1, n) * sizeof(**d)), what);
-      plAllocs_.push_back(*d);
-    };
-    get(&dPlRank_, (size_t)P_, "hipMalloc tie ranks");
-    get(&dPlTopicSel_, (size_t)T_, "hipMalloc topic mask");
-    get(&dPlBrokerSel_, (size_t)B_, "hipMalloc broker mask");
-    get(&dPlBuf_[0], (size_t)P_, "hipMalloc sort buffer");
-    get(&dPlBuf_[1], (size_t)P_, "hipMalloc sort buffer");
-    get(&dPlCounts_, (size_t)256 * (size_t)tiles, "hipMalloc digit counts");
-    get(&dPlState_, 1, "hipMalloc partition load state");  // last: marks the first use done
-  }
-  if ((size_t)cap > plOutCap_) {
-    if (dPlOut_) hipCheck(hipFree(dPlOut_), "hipFree");
-    dPlOut_ = nullptr;
-    plOutCap_ = 0;
-    hipCheck(hipMalloc((void**)&dPlOut_, (size_t)cap * sizeof(ccmi_partition_load_record)), "hipMalloc load records");
-    plOutCap_ = (size_t)cap;
-  }
+  // first use: the query arrays, the sort buffers, the digit counts, the state
+  if (!plWork_) carve(plWork_, [&](Carver& c) { layoutPl(c); });
+  ccmi_partition_load_record* dOut =
+      (ccmi_partition_load_record*)plOut_.ensure((size_t)cap * sizeof(ccmi_partition_load_record));
   // the device's tables current: the pending row updates (prep) and the pending chain loads (sync_loads)
   syncChainLoads();
   if (topicSel)
-    hipCheck(hipMemcpyAsync(dPlTopicSel_, topicSel, (size_t)T_, hipMemcpyHostToDevice, st), "upload topic mask");
+    hipCheck(hipMemcpyAsync(pl_.topicSel, topicSel, (size_t)T_, hipMemcpyHostToDevice, st), "upload topic mask");
   if (brokerSel)
-    hipCheck(hipMemcpyAsync(dPlBrokerSel_, brokerSel, (size_t)B_, hipMemcpyHostToDevice, st), "upload broker mask");
+    hipCheck(hipMemcpyAsync(pl_.brokerSel, brokerSel, (size_t)B_, hipMemcpyHostToDevice, st), "upload broker mask");
   if (tieRank)
-    hipCheck(hipMemcpyAsync(dPlRank_, tieRank, (size_t)P_ * sizeof(int32_t), hipMemcpyHostToDevice, st),
+    hipCheck(hipMemcpyAsync(pl_.rank, tieRank, (size_t)P_ * sizeof(int32_t), hipMemcpyHostToDevice, st),
              "upload tie ranks");
   PlTables T;
   T.parts = parts_;
   T.replicas = replicas_;
   T.rLoad = dRLoad_;
   T.pLeader = dPLeader_;
-  T.pNumber = dPlNumber_;
-  T.topicSel = topicSel ? dPlTopicSel_ : nullptr;
-  T.brokerSel = brokerSel ? dPlBrokerSel_ : nullptr;
-  T.tieRank = tieRank ? dPlRank_ : nullptr;
+  T.pNumber = (const int32_t*)plStatic_.get();
+  T.topicSel = topicSel ? pl_.topicSel : nullptr;
+  T.brokerSel = brokerSel ? pl_.brokerSel : nullptr;
+  T.tieRank = tieRank ? pl_.rank : nullptr;
   T.B = B_;
   T.R = R_;
   T.P = P_;
@@ -361,17 +351,17 @@ void Device::partitionLoad(const PlQuery& q, const uint8_t* topicSel, const uint
   const int slots = (selects ? 1 : 0) + 8 + (tieRank ? 4 : 0);
   int launches = 0;
   timedLaunch([&] {
-    hipCheck(launchPartitionLoad(T, q, dPlState_, dPlBuf_[0], dPlBuf_[1], dPlCounts_, tiles, slots, dPlOut_, cap,
+    hipCheck(launchPartitionLoad(T, q, pl_.state, pl_.buf[0], pl_.buf[1], pl_.counts, tiles, slots, dOut, cap,
                                  &launches, st),
              "partition_load");
   });
   uint32_t head[2] = {0, 0};  // PlState.nKept, nRecords
-  hipCheck(hipMemcpyAsync(head, dPlState_, sizeof(head), hipMemcpyDeviceToHost, st), "D2H partition load counts");
+  hipCheck(hipMemcpyAsync(head, pl_.state, sizeof(head), hipMemcpyDeviceToHost, st), "D2H partition load counts");
   streamWait("partition_load", kAcceptWaitSeconds);
   perf.syncs++;
   const int64_t nrec = std::min<int64_t>(head[1], cap);
   if (nrec > 0) {
-    hipCheck(hipMemcpyAsync(records, dPlOut_, (size_t)nrec * sizeof(ccmi_partition_load_record), hipMemcpyDeviceToHost,
+    hipCheck(hipMemcpyAsync(records, dOut, (size_t)nrec * sizeof(ccmi_partition_load_record), hipMemcpyDeviceToHost,
                             st),
              "D2H load records");
     streamWait("partition_load records", kAcceptWaitSeconds);
@@ -393,51 +383,51 @@ void Device::uploadInitialPlacement(const int32_t* initDist, const int32_t* init
                                     const int32_t* initLeaderDisks) {
   DeviceGuard cur(ordinal_);
   stopServer();
-  if (dPdInitDist_) throw std::logic_error("uploadInitialPlacement: once per session");
+  if (pdStatic_) throw std::logic_error("uploadInitialPlacement: once per session");
   if (P_ < 1 || R_ < 1 || !initDist || !initLeaders || (D_ > 0 && (!initDisks || !initLeaderDisks)))
     throw std::logic_error("uploadInitialPlacement: arguments");
-  auto put = [&](int32_t** d, const int32_t* h, size_t n, const char* what) {
-    hipCheck(hipMalloc((void**)d, n * sizeof(int32_t)), what);
-    pdAllocs_.push_back(*d);
-    hipCheck(hipMemcpy(*d, h, n * sizeof(int32_t), hipMemcpyHostToDevice), what);
-  };
-  put(&dPdInitLeaders_, initLeaders, (size_t)P_, "upload initial leaders");
+  DevBuf block;  // becomes pdStatic_ once every table is up: initialPlacementUploaded()
+  carve(block, [&](Carver& c) { layoutPdStatic(c); });
+  upload(pdInit_.initLeaders, initLeaders, (size_t)P_, "upload initial leaders");
   if (D_ > 0) {
-    put(&dPdInitDisks_, initDisks, (size_t)R_, "upload initial disks");
-    put(&dPdInitLeaderDisks_, initLeaderDisks, (size_t)P_, "upload initial leader disks");
+    upload(pdInit_.initDisks, initDisks, (size_t)R_, "upload initial disks");
+    upload(pdInit_.initLeaderDisks, initLeaderDisks, (size_t)P_, "upload initial leader disks");
   }
-  put(&dPdInitDist_, initDist, (size_t)R_, "upload initial placement");  // last: initialPlacementUploaded()
+  upload(pdInit_.initDist, initDist, (size_t)R_, "upload initial placement");
+  pdStatic_ = std::move(block);
+}
+
+void Device::layoutPdStatic(Carver& c) {
+  c.take(pdInit_.initLeaders, (size_t)P_);
+  if (D_ > 0) {
+    c.take(pdInit_.initDisks, (size_t)R_);
+    c.take(pdInit_.initLeaderDisks, (size_t)P_);
+  }
+  c.take(pdInit_.initDist, (size_t)R_);
+}
+
+void Device::layoutPd(Carver& c) {
+  c.take(pd_.counts, (size_t)((P_ + kPdTile - 1) / kPdTile) + 1);
+  if (D_ > 0) c.take(pd_.curDisks, (size_t)R_);
+  c.take(pd_.sums, 1);
 }
 
 void Device::proposalDiff(const int32_t* curDisks, ccmi_proposal_record* records, int64_t capacity, int64_t* numRecords,
                           ccmi_proposal_summary* summary) {
   PlainLaunch call(*this);
-  if (!dPdInitDist_) throw std::logic_error("proposalDiff before uploadInitialPlacement");
+  if (!pdStatic_) throw std::logic_error("proposalDiff before uploadInitialPlacement");
   if (!numRecords || capacity < 0 || (D_ > 0) != (curDisks != nullptr)) throw std::logic_error("proposalDiff: arguments");
   const int cap = (int)std::min<int64_t>(capacity, P_);
   if (cap > 0 && !records) throw std::logic_error("proposalDiff: no room for the records");
   const hipStream_t st = (hipStream_t)st_;
   const int tiles = (P_ + kPdTile - 1) / kPdTile;
-  if (!dPdSums_) {  // first use: the tile counts, the current disks, the sums
-    auto get = [&](auto** d, size_t n, const char* what) {
-      hipCheck(hipMalloc((void**)d, std::max<size_t>(1, n) * sizeof(**d)), what);
-      pdAllocs_.push_back(*d);
-    };
-    get(&dPdCounts_, (size_t)tiles + 1, "hipMalloc proposal tile counts");
-    if (D_ > 0) get(&dPdCurDisks_, (size_t)R_, "hipMalloc current disks");
-    get(&dPdSums_, 1, "hipMalloc proposal sums");  // last: marks the first use done
-  }
-  if ((size_t)cap > pdOutCap_) {
-    if (dPdOut_) hipCheck(hipFree(dPdOut_), "hipFree");
-    dPdOut_ = nullptr;
-    pdOutCap_ = 0;
-    hipCheck(hipMalloc((void**)&dPdOut_, (size_t)cap * sizeof(ccmi_proposal_record)), "hipMalloc proposal records");
-    pdOutCap_ = (size_t)cap;
-  }
+  // first use: the tile counts, the current disks, the sums
+  if (!pdWork_) carve(pdWork_, [&](Carver& c) { layoutPd(c); });
+  ccmi_proposal_record* dOut = (ccmi_proposal_record*)pdOut_.ensure((size_t)cap * sizeof(ccmi_proposal_record));
   // the device's tables current: the pending row updates (prep) and the pending slot orders and leaders (sync_loads)
   syncChainLoads();
   if (curDisks)
-    hipCheck(hipMemcpyAsync(dPdCurDisks_, curDisks, (size_t)R_ * sizeof(int32_t), hipMemcpyHostToDevice, st),
+    hipCheck(hipMemcpyAsync(pd_.curDisks, curDisks, (size_t)R_ * sizeof(int32_t), hipMemcpyHostToDevice, st),
              "upload current disks");
   PdTables T;
   T.parts = parts_;
@@ -445,25 +435,25 @@ void Device::proposalDiff(const int32_t* curDisks, ccmi_proposal_record* records
   T.pOff = dPOff_;
   T.pSlots = dPSlots_;
   T.pLeader = dPLeader_;
-  T.initDist = dPdInitDist_;
-  T.initLeaders = dPdInitLeaders_;
-  T.initDisks = curDisks ? dPdInitDisks_ : nullptr;
-  T.initLeaderDisks = curDisks ? dPdInitLeaderDisks_ : nullptr;
-  T.curDisks = curDisks ? dPdCurDisks_ : nullptr;
+  T.initDist = pdInit_.initDist;
+  T.initLeaders = pdInit_.initLeaders;
+  T.initDisks = curDisks ? pdInit_.initDisks : nullptr;
+  T.initLeaderDisks = curDisks ? pdInit_.initLeaderDisks : nullptr;
+  T.curDisks = curDisks ? pd_.curDisks : nullptr;
   T.R = R_;
   T.P = P_;
   int launches = 0;
   timedLaunch([&] {
-    hipCheck(launchProposalDiff(T, dPdCounts_, tiles, dPdSums_, dPdOut_, cap, &launches, st), "proposal_diff");
+    hipCheck(launchProposalDiff(T, pd_.counts, tiles, pd_.sums, dOut, cap, &launches, st), "proposal_diff");
   });
   static_assert(sizeof(PdSums) == sizeof(ccmi_proposal_summary), "the device sums are the summary");
   ccmi_proposal_summary sum;
-  hipCheck(hipMemcpyAsync(&sum, dPdSums_, sizeof(sum), hipMemcpyDeviceToHost, st), "D2H proposal summary");
+  hipCheck(hipMemcpyAsync(&sum, pd_.sums, sizeof(sum), hipMemcpyDeviceToHost, st), "D2H proposal summary");
   streamWait("proposal_diff", kAcceptWaitSeconds);
   perf.syncs++;
   const int64_t nrec = std::min<int64_t>(sum.num_proposals, cap);
   if (nrec > 0) {
-    hipCheck(hipMemcpyAsync(records, dPdOut_, (size_t)nrec * sizeof(ccmi_proposal_record), hipMemcpyDeviceToHost, st),
+    hipCheck(hipMemcpyAsync(records, dOut, (size_t)nrec * sizeof(ccmi_proposal_record), hipMemcpyDeviceToHost, st),
              "D2H proposal records");
     streamWait("proposal_diff records", kAcceptWaitSeconds);
     perf.syncs++;
@@ -486,51 +476,51 @@ void Device::proposalDiff(const int32_t* curDisks, ccmi_proposal_record* records
 void Device::uploadSortedStatic(const int32_t* rStatic) {
   DeviceGuard cur(ordinal_);
   stopServer();
-  if (dSrStatic_) throw std::logic_error("uploadSortedStatic: once per session");
+  if (srStatic_) throw std::logic_error("uploadSortedStatic: once per session");
   if (R_ < 1 || B_ < 1 || !rStatic) throw std::logic_error("uploadSortedStatic: arguments");
-  auto get = [&](auto** d, size_t n, const char* what) {
-    hipCheck(hipMalloc((void**)d, std::max<size_t>(1, n) * sizeof(**d)), what);
-    srAllocs_.push_back(*d);
-  };
-  get(&dSrSeg_, (size_t)B_, "hipMalloc segment map");
-  get(&dSrCounts_, (size_t)B_, "hipMalloc segment counts");
-  get(&dSrCursor_, (size_t)B_, "hipMalloc segment cursors");
-  get(&dSrState_, (size_t)B_ + 3, "hipMalloc segment offsets");
-  get(&dSrTopicExcl_, (size_t)T_, "hipMalloc excluded topics");
-  get(&dSrTopicIncl_, (size_t)T_, "hipMalloc included topics");
-  get(&dSrKeys_, (size_t)R_, "hipMalloc replica keys");
-  get(&dSrSegOf_, (size_t)R_, "hipMalloc replica segments");
-  get(&dSrBuf_[0], (size_t)R_, "hipMalloc sort entries");
-  int32_t* d = nullptr;
-  get(&d, (size_t)R_, "hipMalloc static ranks");
-  hipCheck(hipMemcpy(d, rStatic, (size_t)R_ * sizeof(int32_t), hipMemcpyHostToDevice), "upload static ranks");
-  dSrStatic_ = d;  // last: sortedStaticUploaded()
+  DevBuf block;  // becomes srStatic_ once the ranks are up: sortedStaticUploaded()
+  carve(block, [&](Carver& c) { layoutSr(c); });
+  upload(sr_.rStatic, rStatic, (size_t)R_, "upload static ranks");
+  srStatic_ = std::move(block);
+}
+
+void Device::layoutSr(Carver& c) {
+  c.take(sr_.seg, (size_t)B_);
+  c.take(sr_.counts, (size_t)B_);
+  c.take(sr_.cursor, (size_t)B_);
+  c.take(sr_.state, (size_t)B_ + 3);
+  c.take(sr_.topicExcl, (size_t)T_);
+  c.take(sr_.topicIncl, (size_t)T_);
+  c.take(sr_.keys, (size_t)R_);
+  c.take(sr_.segOf, (size_t)R_);
+  c.take(sr_.buf, (size_t)R_);
+  c.take(sr_.rStatic, (size_t)R_);
 }
 
 void Device::sortedReplicas(const SrQuery& q, const int32_t* seg, int n, const uint8_t* topicExcluded,
                             const uint8_t* topicIncluded, int64_t* offsets, ccmi_swap_replica* records, double* scores,
                             int64_t capacity, int64_t* numRecords) {
   PlainLaunch call(*this);
-  if (!dSrStatic_) throw std::logic_error("sortedReplicas before uploadSortedStatic");
+  if (!srStatic_) throw std::logic_error("sortedReplicas before uploadSortedStatic");
   if (!seg || n < 1 || n > B_ || !offsets || !numRecords || capacity < 0)
     throw std::logic_error("sortedReplicas: arguments");
   const hipStream_t st = (hipStream_t)st_;
   // the device's tables current: the pending row updates (prep) and the pending chain loads (sync_loads)
   syncChainLoads();
-  hipCheck(hipMemcpyAsync(dSrSeg_, seg, (size_t)B_ * sizeof(int32_t), hipMemcpyHostToDevice, st), "upload segment map");
+  hipCheck(hipMemcpyAsync(sr_.seg, seg, (size_t)B_ * sizeof(int32_t), hipMemcpyHostToDevice, st), "upload segment map");
   if (topicExcluded)
-    hipCheck(hipMemcpyAsync(dSrTopicExcl_, topicExcluded, (size_t)T_, hipMemcpyHostToDevice, st), "upload excluded topics");
+    hipCheck(hipMemcpyAsync(sr_.topicExcl, topicExcluded, (size_t)T_, hipMemcpyHostToDevice, st), "upload excluded topics");
   if (topicIncluded)
-    hipCheck(hipMemcpyAsync(dSrTopicIncl_, topicIncluded, (size_t)T_, hipMemcpyHostToDevice, st), "upload included topics");
+    hipCheck(hipMemcpyAsync(sr_.topicIncl, topicIncluded, (size_t)T_, hipMemcpyHostToDevice, st), "upload included topics");
   SrTables T;
   T.brokers = brokers_;
   T.replicas = replicas_;
   T.parts = parts_;
   T.rLoad = dRLoad_;
-  T.rStatic = dSrStatic_;
-  T.seg = dSrSeg_;
-  T.topicExcluded = topicExcluded ? dSrTopicExcl_ : nullptr;
-  T.topicIncluded = topicIncluded ? dSrTopicIncl_ : nullptr;
+  T.rStatic = sr_.rStatic;
+  T.seg = sr_.seg;
+  T.topicExcluded = topicExcluded ? sr_.topicExcl : nullptr;
+  T.topicIncluded = topicIncluded ? sr_.topicIncl : nullptr;
   T.B = B_;
   T.R = R_;
   T.P = P_;
@@ -538,12 +528,12 @@ void Device::sortedReplicas(const SrQuery& q, const int32_t* seg, int n, const u
   T.W = W_;
   int launches = 0;
   timedLaunch([&] {
-    hipCheck(launchSortedReplicasCount(T, q, n, dSrKeys_, dSrSegOf_, dSrCounts_, dSrCursor_, dSrState_, &launches, st),
+    hipCheck(launchSortedReplicasCount(T, q, n, sr_.keys, sr_.segOf, sr_.counts, sr_.cursor, sr_.state, &launches, st),
              "sorted_replicas keys");
   });
   // one small read-back: the total, the longest segment and the offsets, which the caller gets whatever the capacity
   srHost_.resize((size_t)n + 3);
-  hipCheck(hipMemcpyAsync(srHost_.data(), dSrState_, ((size_t)n + 3) * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+  hipCheck(hipMemcpyAsync(srHost_.data(), sr_.state, ((size_t)n + 3) * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                           st),
            "D2H segment offsets");
   streamWait("sorted_replicas keys", kAcceptWaitSeconds);
@@ -559,31 +549,25 @@ void Device::sortedReplicas(const SrQuery& q, const int32_t* seg, int n, const u
                      (int64_t)n * 24;
   if (total > 0 && total <= capacity) {
     if (!records) throw std::logic_error("sortedReplicas: no room for the records");
-    if (maxLen > kSegSortTile && !dSrBuf_[1]) {  // a segment longer than a tile: the merge passes' second buffer
-      hipCheck(hipMalloc((void**)&dSrBuf_[1], (size_t)R_ * sizeof(SortEntry)), "hipMalloc merge buffer");
-      srAllocs_.push_back(dSrBuf_[1]);
-    }
-    if ((size_t)total > srOutCap_) {
-      if (dSrRecords_) hipCheck(hipFree(dSrRecords_), "hipFree");
-      if (dSrScores_) hipCheck(hipFree(dSrScores_), "hipFree");
-      dSrRecords_ = nullptr;
-      dSrScores_ = nullptr;
-      srOutCap_ = 0;
-      const size_t room = ((size_t)total + 1) & ~(size_t)1;  // whole 16-byte stores
-      hipCheck(hipMalloc((void**)&dSrRecords_, room * sizeof(ccmi_swap_replica)), "hipMalloc sorted records");
-      hipCheck(hipMalloc((void**)&dSrScores_, room * sizeof(double)), "hipMalloc sorted scores");
-      srOutCap_ = (size_t)total;
-    }
+    // a segment longer than a tile: the merge passes' second buffer, from then on
+    if (maxLen > kSegSortTile) srMerge_.ensure((size_t)R_ * sizeof(SortEntry));
+    // records and scores grow together; the gather's whole 16-byte stores stay inside the pieces' rounding
+    ccmi_swap_replica* dRecords;
+    double* dScores;
+    carve(srOut_, [&](Carver& c) {
+      c.take(dRecords, (size_t)total);
+      c.take(dScores, (size_t)total);
+    });
     int fill = 0;
     timedLaunch([&] {
-      hipCheck(launchSortedReplicasFill(T, q, n, dSrKeys_, dSrSegOf_, dSrCursor_, dSrState_, total, maxLen, dSrBuf_[0],
-                                        dSrBuf_[1], dSrRecords_, scores ? dSrScores_ : nullptr, &fill, st),
+      hipCheck(launchSortedReplicasFill(T, q, n, sr_.keys, sr_.segOf, sr_.cursor, sr_.state, total, maxLen, sr_.buf,
+                                        (SortEntry*)srMerge_.get(), dRecords, scores ? dScores : nullptr, &fill, st),
                "sorted_replicas sort");
     });
-    hipCheck(hipMemcpyAsync(records, dSrRecords_, (size_t)total * sizeof(ccmi_swap_replica), hipMemcpyDeviceToHost, st),
+    hipCheck(hipMemcpyAsync(records, dRecords, (size_t)total * sizeof(ccmi_swap_replica), hipMemcpyDeviceToHost, st),
              "D2H sorted records");
     if (scores)
-      hipCheck(hipMemcpyAsync(scores, dSrScores_, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, st),
+      hipCheck(hipMemcpyAsync(scores, dScores, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, st),
                "D2H sorted scores");
     streamWait("sorted_replicas sort", kAcceptWaitSeconds);
     perf.syncs++;
@@ -596,75 +580,74 @@ void Device::sortedReplicas(const SrQuery& q, const int32_t* seg, int n, const u
   perf.statsLaunches += launches;
 }
 
+void Device::layoutEp(Carver& c) {
+  const size_t tiles = (size_t)((P_ + kPdTile - 1) / kPdTile);
+  c.take(ep_.rows, (size_t)P_);
+  c.take(ep_.idOf, (size_t)P_);
+  c.take(ep_.rank, (size_t)P_);
+  c.take(ep_.pstate, (size_t)P_);
+  if (D_ > 0) c.take(ep_.curDisks, (size_t)R_);
+  c.take(ep_.order, (size_t)B_);
+  c.take(ep_.tiles, 2 * (tiles + 1));
+  c.take(ep_.counts, 2 * (size_t)B_);
+  c.take(ep_.cursors, 2 * (size_t)B_);
+  c.take(ep_.state, 2 * ((size_t)B_ + 3) + 4);
+  c.take(ep_.sums, 1);
+}
+
 void Device::executionPlan(const EpQuery& q, const int32_t* curDisks, const int32_t* rank, const uint8_t* state,
                            ccmi_plan_summary* summary, ccmi_plan_task* tasks, int64_t taskCap, int64_t* interOffsets,
                            int32_t* interEntries, int64_t interCap, int32_t* brokerOrder, int64_t* intraOffsets,
                            int32_t* intraEntries, int64_t intraCap, int32_t* leaderTasks, int64_t leaderCap) {
   PlainLaunch call(*this);
-  if (!dPdInitDist_) throw std::logic_error("executionPlan before uploadInitialPlacement");
+  if (!pdStatic_) throw std::logic_error("executionPlan before uploadInitialPlacement");
   if (!summary || !interOffsets || !intraOffsets || taskCap < 0 || interCap < 0 || intraCap < 0 || leaderCap < 0 ||
       (D_ > 0) != (curDisks != nullptr) || P_ < 1 || B_ < 1)
     throw std::logic_error("executionPlan: arguments");
   const hipStream_t st = (hipStream_t)st_;
   const int tiles = (P_ + kPdTile - 1) / kPdTile;
   const size_t stateWords = 2 * ((size_t)B_ + 3) + 4;
-  if (!dEpSums_) {  // first use
-    auto get = [&](auto** d, size_t n, const char* what) {
-      hipCheck(hipMalloc((void**)d, std::max<size_t>(1, n) * sizeof(**d)), what);
-      epAllocs_.push_back(*d);
-    };
-    get(&dEpRows_, (size_t)P_, "hipMalloc plan rows");
-    get(&dEpIdOf_, (size_t)P_, "hipMalloc execution ids");
-    get(&dEpRank_, (size_t)P_, "hipMalloc proposal ranks");
-    get(&dEpPState_, (size_t)P_, "hipMalloc partition states");
-    if (D_ > 0) get(&dEpCurDisks_, (size_t)R_, "hipMalloc current disks");
-    get(&dEpOrder_, (size_t)B_, "hipMalloc broker order");
-    get(&dEpTiles_, 2 * ((size_t)tiles + 1), "hipMalloc plan tile counts");
-    get(&dEpCounts_, 2 * (size_t)B_, "hipMalloc plan broker counts");
-    get(&dEpCursors_, 2 * (size_t)B_, "hipMalloc plan cursors");
-    get(&dEpState_, stateWords, "hipMalloc plan offsets");
-    get(&dEpSums_, 1, "hipMalloc plan sums");  // last: marks the first use done
-  }
+  if (!epWork_) carve(epWork_, [&](Carver& c) { layoutEp(c); });  // first use
   // the device's tables current: the pending row updates (prep) and the pending slot orders and leaders (sync_loads)
   syncChainLoads();
   if (curDisks)
-    hipCheck(hipMemcpyAsync(dEpCurDisks_, curDisks, (size_t)R_ * sizeof(int32_t), hipMemcpyHostToDevice, st),
+    hipCheck(hipMemcpyAsync(ep_.curDisks, curDisks, (size_t)R_ * sizeof(int32_t), hipMemcpyHostToDevice, st),
              "upload current disks");
   if (rank)
-    hipCheck(hipMemcpyAsync(dEpRank_, rank, (size_t)P_ * sizeof(int32_t), hipMemcpyHostToDevice, st),
+    hipCheck(hipMemcpyAsync(ep_.rank, rank, (size_t)P_ * sizeof(int32_t), hipMemcpyHostToDevice, st),
              "upload proposal ranks");
   if (state)
-    hipCheck(hipMemcpyAsync(dEpPState_, state, (size_t)P_, hipMemcpyHostToDevice, st), "upload partition states");
+    hipCheck(hipMemcpyAsync(ep_.pstate, state, (size_t)P_, hipMemcpyHostToDevice, st), "upload partition states");
   EpTables T;
   T.pd.parts = parts_;
   T.pd.replicas = replicas_;
   T.pd.pOff = dPOff_;
   T.pd.pSlots = dPSlots_;
   T.pd.pLeader = dPLeader_;
-  T.pd.initDist = dPdInitDist_;
-  T.pd.initLeaders = dPdInitLeaders_;
-  T.pd.initDisks = curDisks ? dPdInitDisks_ : nullptr;
-  T.pd.initLeaderDisks = curDisks ? dPdInitLeaderDisks_ : nullptr;
-  T.pd.curDisks = curDisks ? dEpCurDisks_ : nullptr;
+  T.pd.initDist = pdInit_.initDist;
+  T.pd.initLeaders = pdInit_.initLeaders;
+  T.pd.initDisks = curDisks ? pdInit_.initDisks : nullptr;
+  T.pd.initLeaderDisks = curDisks ? pdInit_.initLeaderDisks : nullptr;
+  T.pd.curDisks = curDisks ? ep_.curDisks : nullptr;
   T.pd.R = R_;
   T.pd.P = P_;
-  T.rank = rank ? dEpRank_ : nullptr;
-  T.state = state ? dEpPState_ : nullptr;
+  T.rank = rank ? ep_.rank : nullptr;
+  T.state = state ? ep_.pstate : nullptr;
   T.B = B_;
-  uint32_t* tileInter = dEpTiles_;
-  uint32_t* tileLeader = dEpTiles_ + tiles + 1;
+  uint32_t* tileInter = ep_.tiles;
+  uint32_t* tileLeader = ep_.tiles + tiles + 1;
   int launches = 0;
   timedLaunch([&] {
-    hipCheck(launchExecutionPlanCount(T, tiles, dEpRows_, tileInter, tileLeader, dEpCounts_, dEpCursors_, dEpSums_,
-                                      dEpState_, &launches, st),
+    hipCheck(launchExecutionPlanCount(T, tiles, ep_.rows, tileInter, tileLeader, ep_.counts, ep_.cursors, ep_.sums,
+                                      ep_.state, &launches, st),
              "execution_plan classify");
   });
   // one small read-back: the sums, and both lists' totals, longest segments and offsets, which the caller gets whatever
   // the capacities
   EpSums sums;
   epHost_.resize(stateWords);
-  hipCheck(hipMemcpyAsync(&sums, dEpSums_, sizeof(sums), hipMemcpyDeviceToHost, st), "D2H plan sums");
-  hipCheck(hipMemcpyAsync(epHost_.data(), dEpState_, stateWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st),
+  hipCheck(hipMemcpyAsync(&sums, ep_.sums, sizeof(sums), hipMemcpyDeviceToHost, st), "D2H plan sums");
+  hipCheck(hipMemcpyAsync(epHost_.data(), ep_.state, stateWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st),
            "D2H plan offsets");
   streamWait("execution_plan classify", kAcceptWaitSeconds);
   perf.syncs++;
@@ -705,42 +688,32 @@ void Device::executionPlan(const EpQuery& q, const int32_t* curDisks, const int3
     if ((numTasks > 0 && !tasks) || (interTotal > 0 && (!interEntries || !brokerOrder)) ||
         (intraTotal > 0 && !intraEntries) || (numLeader > 0 && !leaderTasks))
       throw std::logic_error("executionPlan: no room for the lists");
-    auto grow = [&](auto** d, size_t& cap, size_t need, size_t round, const char* what) {
-      if (need <= cap) return;
-      if (*d) hipCheck(hipFree(*d), "hipFree");
-      *d = nullptr;
-      cap = 0;
-      const size_t room = (need + round - 1) / round * round;  // whole 16-byte stores
-      hipCheck(hipMalloc((void**)d, room * sizeof(**d)), what);
-      cap = need;
-    };
-    if ((size_t)entries > epBufCap_) {  // both buffers: a merge pass may come with any call
-      size_t cap0 = 0;
-      grow(&dEpBuf_[0], cap0, (size_t)entries, 1, "hipMalloc plan entries");
-      cap0 = 0;
-      grow(&dEpBuf_[1], cap0, (size_t)entries, 1, "hipMalloc plan merge buffer");
-      epBufCap_ = (size_t)entries;
-    }
-    grow(&dEpTasks_, epTaskCap_, (size_t)numTasks, 1, "hipMalloc plan tasks");
-    grow(&dEpInterOut_, epInterCap_, (size_t)interTotal, 4, "hipMalloc plan inter entries");
-    grow(&dEpIntraOut_, epIntraCap_, (size_t)intraTotal, 4, "hipMalloc plan intra entries");
-    grow(&dEpLeaderOut_, epLeaderCap_, (size_t)numLeader, 4, "hipMalloc plan leader tasks");
+    // the gathers finish a list with whole 16-byte stores: a DevBuf's capacity is whole 256-byte runs
+    SortEntry* buf[2];  // both buffers in one block: a merge pass may come with any call
+    carve(epEntries_, [&](Carver& c) {
+      c.take(buf[0], (size_t)entries);
+      c.take(buf[1], (size_t)entries);
+    });
+    ccmi_plan_task* dTasks = (ccmi_plan_task*)epTasks_.ensure((size_t)numTasks * sizeof(ccmi_plan_task));
+    int32_t* dInter = (int32_t*)epInter_.ensure((size_t)interTotal * sizeof(int32_t));
+    int32_t* dIntra = (int32_t*)epIntra_.ensure((size_t)intraTotal * sizeof(int32_t));
+    int32_t* dLeader = (int32_t*)epLeader_.ensure((size_t)numLeader * sizeof(int32_t));
     int fill = 0;
     timedLaunch([&] {
-      hipCheck(launchExecutionPlanFill(T, q, tiles, dEpRows_, tileInter, tileLeader, dEpCursors_, dEpState_, numTasks,
-                                       numLeader, interTotal, interMax, intraTotal, intraMax, dEpBuf_[0], dEpBuf_[1],
-                                       dEpIdOf_, dEpTasks_, dEpInterOut_, dEpOrder_, dEpIntraOut_, dEpLeaderOut_, &fill,
+      hipCheck(launchExecutionPlanFill(T, q, tiles, ep_.rows, tileInter, tileLeader, ep_.cursors, ep_.state, numTasks,
+                                       numLeader, interTotal, interMax, intraTotal, intraMax, buf[0], buf[1],
+                                       ep_.idOf, dTasks, dInter, ep_.order, dIntra, dLeader, &fill,
                                        st),
                "execution_plan fill");
     });
     auto back = [&](void* h, const void* d, size_t bytes, const char* what) {
       if (bytes) hipCheck(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, st), what);
     };
-    back(tasks, dEpTasks_, (size_t)numTasks * sizeof(ccmi_plan_task), "D2H plan tasks");
-    back(interEntries, dEpInterOut_, (size_t)interTotal * sizeof(int32_t), "D2H plan inter entries");
-    if (interTotal > 0) back(brokerOrder, dEpOrder_, (size_t)B_ * sizeof(int32_t), "D2H broker order");
-    back(intraEntries, dEpIntraOut_, (size_t)intraTotal * sizeof(int32_t), "D2H plan intra entries");
-    back(leaderTasks, dEpLeaderOut_, (size_t)numLeader * sizeof(int32_t), "D2H plan leader tasks");
+    back(tasks, dTasks, (size_t)numTasks * sizeof(ccmi_plan_task), "D2H plan tasks");
+    back(interEntries, dInter, (size_t)interTotal * sizeof(int32_t), "D2H plan inter entries");
+    if (interTotal > 0) back(brokerOrder, ep_.order, (size_t)B_ * sizeof(int32_t), "D2H broker order");
+    back(intraEntries, dIntra, (size_t)intraTotal * sizeof(int32_t), "D2H plan intra entries");
+    back(leaderTasks, dLeader, (size_t)numLeader * sizeof(int32_t), "D2H plan leader tasks");
     streamWait("execution_plan fill", kAcceptWaitSeconds);
     perf.syncs++;
     addKernelMs(perf.statsKernelMs);

@@ -1,5 +1,7 @@
-// hipCheck and DeviceGuard for the translation units that call the HIP runtime (device.cpp, device_accept.cpp). Product
-// only: the test emulation of Device has no HIP and does not include this.
+// hipCheck and DeviceGuard for the translation units that call the HIP runtime (device.cpp, device_accept.cpp and the
+// aggregator family: ccmi_aggregator.cpp, ccmi_load_model.cpp, ccmi_anomaly.cpp). Owning device and pinned memory is
+// not done here: devbuf.h has the buffers, device.cpp the four HIP calls behind them. Product only: the test emulation
+// of Device has no HIP and does not include this.
 #pragma once
 #include <hip/hip_runtime.h>
 

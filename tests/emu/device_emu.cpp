@@ -134,6 +134,12 @@ int Device::countGfx950() {  // one emulated device, or CCMI_EMU_DEVICES (tests 
 }
 bool deviceLocalCpuList(int, std::string&) { return false; }  // no PCI device
 
+// devbuf.h: the emulation has none of the query buffers, so nothing may ask for one
+void* deviceAlloc(size_t) { throw std::logic_error("the Device emulation has no device buffers"); }
+void deviceFree(void*) noexcept {}
+void* pinnedAlloc(size_t) { throw std::logic_error("the Device emulation has no pinned buffers"); }
+void pinnedFree(void*) noexcept {}
+
 Device::Device(int ordinal, int B, int R, int P, int T, int maxGoalSlots)
     : ordinal_(ordinal), B_(B), R_(R), P_(P), T_(T), ldB_((B + 3) & ~3), G_(maxGoalSlots) {
   auto* e = new Emu();

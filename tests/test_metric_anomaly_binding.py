@@ -81,7 +81,7 @@ def test_sources_and_documents():
     kernel = _read("cruise-control_amd", "csrc", "kernels", "anomaly.hip")
     assert '#include "../engine/percentile.h"' in kernel and '#include "segments.h"' in kernel
     assert '#include "percentile.h"' in _read("tests", "cpp", "test_percentile.cpp")
-    assert "DBuf* target" in _read("cruise-control_amd", "csrc", "ccmi_aggregator_impl.h")
+    assert "DevBuf* target" in _read("cruise-control_amd", "csrc", "ccmi_aggregator_impl.h")
     for doc in ("README.md", "DESIGN.md", "INTEGRATION.md"):
         text = _read(doc)
         assert "ccmi_aggregator_metric_anomalies" in text and "ccmi_slow_broker_finder" in text, doc
