@@ -362,6 +362,68 @@ class SlowBrokerStruct(C.Structure):  # ccmi_slow_broker, 24 bytes
                 ("since_ms", C.c_int64)]
 
 
+class MetricsProcessorConfigStruct(C.Structure):  # ccmi_metrics_processor_config, 32 bytes
+    _fields_ = [("cpu_weight_of_leader_bytes_in_rate", C.c_double), ("cpu_weight_of_leader_bytes_out_rate", C.c_double),
+                ("cpu_weight_of_follower_bytes_in_rate", C.c_double), ("reserved", C.c_int64)]
+
+
+class RawMetricsStruct(C.Structure):  # ccmi_raw_metrics, 72 bytes
+    _fields_ = [("n", C.c_int64), ("num_topics", C.c_int32), ("reserved", C.c_int32),
+                ("topic_names", C.POINTER(C.c_char_p)), ("type", C.c_void_p), ("broker_id", C.c_void_p),
+                ("time_ms", C.c_void_p), ("value", C.c_void_p), ("topic", C.c_void_p), ("partition", C.c_void_p)]
+
+
+class ClusterNodesStruct(C.Structure):  # ccmi_cluster_nodes, 24 bytes
+    _fields_ = [("num_nodes", C.c_int32), ("reserved", C.c_int32), ("broker_id", C.c_void_p),
+                ("num_cores", C.c_void_p)]
+
+
+class ProcessedSamplesStruct(C.Structure):  # ccmi_processed_samples, 120 bytes
+    _fields_ = [("max_metric_timestamp", C.c_int64), ("partition_capacity", C.c_int64),
+                ("num_partition_samples", C.c_int64), ("partition_entity", C.c_void_p),
+                ("partition_values", C.c_void_p), ("broker_capacity", C.c_int64), ("num_broker_samples", C.c_int64),
+                ("broker_node", C.c_void_p), ("broker_values", C.c_void_p), ("broker_version", C.c_void_p),
+                ("partition_skip", C.c_void_p), ("broker_skip", C.c_void_p), ("skipped_by_node", C.c_void_p),
+                ("num_skipped_brokers", C.c_int32), ("num_hash_fallback_brokers", C.c_int32),
+                ("num_dropped_records", C.c_int64)]
+
+
+METRICS_PROCESSOR_SYMBOLS = ("ccmi_metrics_processor_create", "ccmi_metrics_processor_destroy",
+                             "ccmi_metrics_processor_add_metrics", "ccmi_metrics_processor_process",
+                             "ccmi_metrics_processor_process_into", "ccmi_metrics_processor_cached_num_cores", "ccmi_metrics_processor_clear")
+# RawMetricType in id order (cruise-control-metrics-reporter, RawMetricType.java); index = id
+RAW_METRIC_TYPES = (
+    "ALL_TOPIC_BYTES_IN", "ALL_TOPIC_BYTES_OUT", "TOPIC_BYTES_IN", "TOPIC_BYTES_OUT", "PARTITION_SIZE",
+    "BROKER_CPU_UTIL", "ALL_TOPIC_REPLICATION_BYTES_IN", "ALL_TOPIC_REPLICATION_BYTES_OUT",
+    "ALL_TOPIC_PRODUCE_REQUEST_RATE", "ALL_TOPIC_FETCH_REQUEST_RATE", "ALL_TOPIC_MESSAGES_IN_PER_SEC",
+    "TOPIC_REPLICATION_BYTES_IN", "TOPIC_REPLICATION_BYTES_OUT", "TOPIC_PRODUCE_REQUEST_RATE",
+    "TOPIC_FETCH_REQUEST_RATE", "TOPIC_MESSAGES_IN_PER_SEC", "BROKER_PRODUCE_REQUEST_RATE",
+    "BROKER_CONSUMER_FETCH_REQUEST_RATE", "BROKER_FOLLOWER_FETCH_REQUEST_RATE",
+    "BROKER_REQUEST_HANDLER_AVG_IDLE_PERCENT", "BROKER_REQUEST_QUEUE_SIZE", "BROKER_RESPONSE_QUEUE_SIZE",
+    "BROKER_PRODUCE_REQUEST_QUEUE_TIME_MS_MAX", "BROKER_PRODUCE_REQUEST_QUEUE_TIME_MS_MEAN",
+    "BROKER_CONSUMER_FETCH_REQUEST_QUEUE_TIME_MS_MAX", "BROKER_CONSUMER_FETCH_REQUEST_QUEUE_TIME_MS_MEAN",
+    "BROKER_FOLLOWER_FETCH_REQUEST_QUEUE_TIME_MS_MAX", "BROKER_FOLLOWER_FETCH_REQUEST_QUEUE_TIME_MS_MEAN",
+    "BROKER_PRODUCE_TOTAL_TIME_MS_MAX", "BROKER_PRODUCE_TOTAL_TIME_MS_MEAN",
+    "BROKER_CONSUMER_FETCH_TOTAL_TIME_MS_MAX", "BROKER_CONSUMER_FETCH_TOTAL_TIME_MS_MEAN",
+    "BROKER_FOLLOWER_FETCH_TOTAL_TIME_MS_MAX", "BROKER_FOLLOWER_FETCH_TOTAL_TIME_MS_MEAN",
+    "BROKER_PRODUCE_LOCAL_TIME_MS_MAX", "BROKER_PRODUCE_LOCAL_TIME_MS_MEAN",
+    "BROKER_CONSUMER_FETCH_LOCAL_TIME_MS_MAX", "BROKER_CONSUMER_FETCH_LOCAL_TIME_MS_MEAN",
+    "BROKER_FOLLOWER_FETCH_LOCAL_TIME_MS_MAX", "BROKER_FOLLOWER_FETCH_LOCAL_TIME_MS_MEAN",
+    "BROKER_LOG_FLUSH_RATE", "BROKER_LOG_FLUSH_TIME_MS_MAX", "BROKER_LOG_FLUSH_TIME_MS_MEAN",
+    "BROKER_PRODUCE_REQUEST_QUEUE_TIME_MS_50TH", "BROKER_PRODUCE_REQUEST_QUEUE_TIME_MS_999TH",
+    "BROKER_CONSUMER_FETCH_REQUEST_QUEUE_TIME_MS_50TH", "BROKER_CONSUMER_FETCH_REQUEST_QUEUE_TIME_MS_999TH",
+    "BROKER_FOLLOWER_FETCH_REQUEST_QUEUE_TIME_MS_50TH", "BROKER_FOLLOWER_FETCH_REQUEST_QUEUE_TIME_MS_999TH",
+    "BROKER_PRODUCE_TOTAL_TIME_MS_50TH", "BROKER_PRODUCE_TOTAL_TIME_MS_999TH",
+    "BROKER_CONSUMER_FETCH_TOTAL_TIME_MS_50TH", "BROKER_CONSUMER_FETCH_TOTAL_TIME_MS_999TH",
+    "BROKER_FOLLOWER_FETCH_TOTAL_TIME_MS_50TH", "BROKER_FOLLOWER_FETCH_TOTAL_TIME_MS_999TH",
+    "BROKER_PRODUCE_LOCAL_TIME_MS_50TH", "BROKER_PRODUCE_LOCAL_TIME_MS_999TH",
+    "BROKER_CONSUMER_FETCH_LOCAL_TIME_MS_50TH", "BROKER_CONSUMER_FETCH_LOCAL_TIME_MS_999TH",
+    "BROKER_FOLLOWER_FETCH_LOCAL_TIME_MS_50TH", "BROKER_FOLLOWER_FETCH_LOCAL_TIME_MS_999TH",
+    "BROKER_LOG_FLUSH_TIME_MS_50TH", "BROKER_LOG_FLUSH_TIME_MS_999TH")
+RAW_METRIC_TYPE_ID = {name: i for i, name in enumerate(RAW_METRIC_TYPES)}
+(SAMPLING_ALL, SAMPLING_BROKER_METRICS_ONLY, SAMPLING_PARTITION_METRICS_ONLY,
+ SAMPLING_ONGOING_EXECUTION) = range(4)  # ccmi_sampling_mode
+
 SLOW_BROKER_DEMOTE, SLOW_BROKER_REMOVE = 1, 2  # ccmi_slow_broker.kind
 # CCMI_SLOW_DIAG_*: the bits of ccmi_slow_broker_finder_detect's per-entity diagnostic byte
 (SLOW_DIAG_SKIPPED, SLOW_DIAG_FLUSH_HISTORY, SLOW_DIAG_FLUSH_PEERS, SLOW_DIAG_PER_BYTE_HISTORY,
@@ -444,7 +506,10 @@ EXPORTED_SYMBOLS = (
     "ccmi_aggregator_completeness_query", "ccmi_aggregator_aggregate", "ccmi_aggregator_peek_current_window",
     "ccmi_aggregator_remove_entities", "ccmi_aggregator_clear", "ccmi_builder_populate_from_aggregator",
     "ccmi_aggregator_metric_anomalies", "ccmi_slow_broker_finder_create", "ccmi_slow_broker_finder_destroy",
-    "ccmi_slow_broker_finder_detect", "ccmi_slow_broker_finder_scores", "ccmi_slow_broker_finder_reset")
+    "ccmi_slow_broker_finder_detect", "ccmi_slow_broker_finder_scores", "ccmi_slow_broker_finder_reset",
+    "ccmi_metrics_processor_create", "ccmi_metrics_processor_destroy", "ccmi_metrics_processor_add_metrics",
+    "ccmi_metrics_processor_process", "ccmi_metrics_processor_process_into", "ccmi_metrics_processor_cached_num_cores",
+    "ccmi_metrics_processor_clear")
 
 # int (*)(void* ctx, int64_t* key): replace *key by the MIN over all shards, return 0 (include/ccmi.h)
 AllreduceMinFn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int64))
@@ -559,6 +624,21 @@ class Library:
             L.ccmi_slow_broker_finder_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
             L.ccmi_slow_broker_finder_reset.argtypes = [C.c_void_p]
         # LoadMonitor.clusterModel's bulk load from an aggregator's device rows (K18): device only as well
+        self.has_metrics_processor = hasattr(L, "ccmi_metrics_processor_create")
+        if self.has_metrics_processor:
+            L.ccmi_metrics_processor_create.argtypes = [C.c_int32, C.POINTER(MetricsProcessorConfigStruct),
+                                                        C.POINTER(C.c_void_p)]
+            L.ccmi_metrics_processor_destroy.argtypes = [C.c_void_p]
+            L.ccmi_metrics_processor_destroy.restype = None
+            L.ccmi_metrics_processor_add_metrics.argtypes = [C.c_void_p, C.POINTER(RawMetricsStruct)]
+            L.ccmi_metrics_processor_process.argtypes = [C.c_void_p, C.POINTER(PartitionTopologyStruct),
+                                                         C.POINTER(ClusterNodesStruct), C.c_void_p, C.c_int32,
+                                                         C.POINTER(ProcessedSamplesStruct)]
+            L.ccmi_metrics_processor_process_into.argtypes = [C.c_void_p, C.POINTER(PartitionTopologyStruct),
+                                                              C.POINTER(ClusterNodesStruct), C.c_void_p, C.c_int32,
+                                                              C.c_void_p, C.c_void_p, C.POINTER(ProcessedSamplesStruct)]
+            L.ccmi_metrics_processor_cached_num_cores.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
+            L.ccmi_metrics_processor_clear.argtypes = [C.c_void_p]
         self.has_load_model = hasattr(L, "ccmi_builder_populate_from_aggregator")
         if self.has_load_model:
             L.ccmi_builder_populate_from_aggregator.argtypes = [
@@ -2105,6 +2185,148 @@ class SlowBrokerFinder:
 
     def reset(self) -> None:
         self.lib.check(self.lib.lib.ccmi_slow_broker_finder_reset(self.handle))
+
+
+class ProcessedSamples:
+    """What MetricsProcessor.process returns: numpy arrays, see ccmi_processed_samples in include/ccmi.h."""
+
+    def __init__(self, s: ProcessedSamplesStruct, arrays):
+        (self.partition_entity, self.partition_values, self.broker_node, self.broker_values, self.broker_version,
+         self.partition_skip, self.broker_skip, self.skipped_by_node) = arrays
+        self.max_metric_timestamp = int(s.max_metric_timestamp)
+        self.num_partition_samples, self.num_broker_samples = int(s.num_partition_samples), int(s.num_broker_samples)
+        self.num_skipped_brokers = int(s.num_skipped_brokers)
+        self.num_hash_fallback_brokers = int(s.num_hash_fallback_brokers)
+        self.num_dropped_records = int(s.num_dropped_records)
+        kp = min(self.num_partition_samples, len(self.partition_entity))
+        kb = min(self.num_broker_samples, len(self.broker_node))
+        self.partition_entity, self.partition_values = self.partition_entity[:kp], self.partition_values[:kp]
+        self.broker_node, self.broker_values = self.broker_node[:kb], self.broker_values[:kb]
+        self.broker_version = self.broker_version[:kb]
+
+
+class MetricsProcessor:
+    """CruiseControlMetricsProcessor on the device (ccmi_metrics_processor_*): one sampling round's raw records in,
+    partition and broker samples out as the rows MetricSampleAggregator.add_samples takes.
+
+        mp = MetricsProcessor()
+        mp.add_metrics(types, broker_ids, times_ms, values, topics, partitions, topic_names)
+        s = mp.process(topic_names, partition_topic, partition_number, replica_offset, leader_broker_id,
+                       node_ids, num_cores)
+        partition_agg.add_samples(s.partition_entity, [s.max_metric_timestamp] * len(s.partition_entity),
+                                  s.partition_values)
+        mp.clear()
+    """
+
+    def __init__(self, cpu_weights: Optional[Sequence[float]] = None, device: int = 0, lib: Optional[Library] = None):
+        self.lib = lib or Library.get()
+        self.handle = None
+        if not self.lib.has_metrics_processor:
+            raise UnsupportedOperationException(f"{self.lib.path} does not export ccmi_metrics_processor_create: "
+                                                "the metrics processor runs on the device only")
+        cfg = None
+        if cpu_weights is not None:
+            a, b, c = (float(x) for x in cpu_weights)
+            cfg = C.byref(MetricsProcessorConfigStruct(a, b, c, 0))
+        h = C.c_void_p()
+        self.lib.check(self.lib.lib.ccmi_metrics_processor_create(device, cfg, C.byref(h)))
+        self.handle = h
+
+    def __del__(self):
+        try:
+            if self.handle:
+                self.lib.lib.ccmi_metrics_processor_destroy(self.handle)
+        except Exception:
+            pass
+
+    def add_metrics(self, types, broker_ids, times_ms, values, topics, partitions, topic_names: Sequence[str]) -> None:
+        """addMetric for every record in order. types: RawMetricType ids (RAW_METRIC_TYPE_ID); topics: index into
+        topic_names or -1; partitions: -1 unless PARTITION_SIZE."""
+        import numpy as np
+
+        ty = np.ascontiguousarray(types, dtype=np.uint8).reshape(-1)
+        br = np.ascontiguousarray(broker_ids, dtype=np.int32).reshape(-1)
+        tm = np.ascontiguousarray(times_ms, dtype=np.int64).reshape(-1)
+        va = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        to = np.ascontiguousarray(topics, dtype=np.int32).reshape(-1)
+        pa = np.ascontiguousarray(partitions, dtype=np.int32).reshape(-1)
+        n = int(ty.size)
+        if any(int(a.size) != n for a in (br, tm, va, to, pa)):
+            raise IllegalArgumentException("the record columns disagree on the number of records")
+        names = (C.c_char_p * max(len(topic_names), 1))(*[t.encode() for t in topic_names])
+        s = RawMetricsStruct(n, len(topic_names), 0, C.cast(names, C.POINTER(C.c_char_p)), ty.ctypes.data,
+                             br.ctypes.data, tm.ctypes.data, va.ctypes.data, to.ctypes.data, pa.ctypes.data)
+        self.lib.check(self.lib.lib.ccmi_metrics_processor_add_metrics(self.handle, C.byref(s)))
+
+    def process(self, topic_names: Sequence[str], partition_topic, partition_number, replica_offset,
+                leader_broker_id, node_ids, num_cores, interested=None, sampling_mode: int = SAMPLING_ALL,
+                partition_capacity: Optional[int] = None, broker_capacity: Optional[int] = None,
+                _into=None) -> ProcessedSamples:
+        """process(cluster, partitions, samplingMode). The cluster: topic names (with their dots), per partition its
+        topic index, number, replica range and leader id (-1: none); the nodes with the resolver's cores (NaN: none)."""
+        import numpy as np
+
+        pt = np.ascontiguousarray(partition_topic, dtype=np.int32).reshape(-1)
+        pn = np.ascontiguousarray(partition_number, dtype=np.int32).reshape(-1)
+        ro = np.ascontiguousarray(replica_offset, dtype=np.int32).reshape(-1)
+        ld = np.ascontiguousarray(leader_broker_id, dtype=np.int32).reshape(-1)
+        ids = np.ascontiguousarray(node_ids, dtype=np.int32).reshape(-1)
+        cores = np.ascontiguousarray(num_cores, dtype=np.float64).reshape(-1)
+        P, N = int(pt.size), int(ids.size)
+        if pn.size != P or ld.size != P or ro.size != P + 1 or cores.size != N:
+            raise IllegalArgumentException("the cluster columns disagree on the number of partitions or nodes")
+        mask = None
+        if interested is not None:
+            mask = np.ascontiguousarray(interested, dtype=np.uint8).reshape(-1)
+            if mask.size != P:
+                raise IllegalArgumentException("the interested mask has one byte per partition")
+        names = (C.c_char_p * max(len(topic_names), 1))(*[t.encode() for t in topic_names])
+        topo = PartitionTopologyStruct()
+        topo.num_partitions, topo.num_topics = P, len(topic_names)
+        topo.topic_names = C.cast(names, C.POINTER(C.c_char_p))
+        topo.partition_topic = pt.ctypes.data_as(C.POINTER(C.c_int32))
+        topo.partition_number = pn.ctypes.data_as(C.POINTER(C.c_int32))
+        topo.replica_offset = ro.ctypes.data_as(C.POINTER(C.c_int32))
+        topo.leader_broker_id = ld.ctypes.data_as(C.POINTER(C.c_int32))
+        nodes = ClusterNodesStruct(N, 0, ids.ctypes.data, cores.ctypes.data)
+        kp = P if partition_capacity is None else int(partition_capacity)
+        kb = N if broker_capacity is None else int(broker_capacity)
+        arrays = [np.zeros(max(kp, 0), dtype=np.int32), np.zeros((max(kp, 0), 9), dtype=np.float64),
+                  np.zeros(max(kb, 0), dtype=np.int32), np.zeros((max(kb, 0), 56), dtype=np.float64),
+                  np.zeros(max(kb, 0), dtype=np.int8), np.zeros(P, dtype=np.uint8), np.zeros(N, dtype=np.uint8),
+                  np.zeros(N + 1, dtype=np.int32)]
+        s = ProcessedSamplesStruct()
+        s.partition_capacity, s.broker_capacity = kp, kb
+        (s.partition_entity, s.partition_values, s.broker_node, s.broker_values, s.broker_version, s.partition_skip,
+         s.broker_skip, s.skipped_by_node) = [a.ctypes.data for a in arrays]
+        if _into is not None:
+            self.lib.check(self.lib.lib.ccmi_metrics_processor_process_into(
+                self.handle, C.byref(topo), C.byref(nodes), mask.ctypes.data if mask is not None else None,
+                int(sampling_mode), *[a.handle if a is not None else None for a in _into], C.byref(s)))
+            s.partition_capacity = s.broker_capacity = 0  # no rows come back
+            return ProcessedSamples(s, [a[:0] for a in arrays[:5]] + arrays[5:])
+        self.lib.check(self.lib.lib.ccmi_metrics_processor_process(
+            self.handle, C.byref(topo), C.byref(nodes), mask.ctypes.data if mask is not None else None,
+            int(sampling_mode), C.byref(s)))
+        return ProcessedSamples(s, arrays)
+
+    def process_into(self, topic_names: Sequence[str], partition_topic, partition_number, replica_offset,
+                     leader_broker_id, node_ids, num_cores, partition_aggregator: Optional[MetricSampleAggregator],
+                     broker_aggregator: Optional[MetricSampleAggregator], interested=None,
+                     sampling_mode: int = SAMPLING_ALL) -> ProcessedSamples:
+        """process, with the rows fed to the aggregators on the device (either may be None) instead of returned: the
+        result has the counts and the skip tables only."""
+        return self.process(topic_names, partition_topic, partition_number, replica_offset, leader_broker_id, node_ids,
+                            num_cores, interested=interested, sampling_mode=sampling_mode,
+                            _into=(partition_aggregator, broker_aggregator))
+
+    def cached_num_cores(self, broker_id: int) -> Optional[float]:
+        v = C.c_double(0.0)
+        self.lib.check(self.lib.lib.ccmi_metrics_processor_cached_num_cores(self.handle, int(broker_id), C.byref(v)))
+        return None if v.value != v.value else v.value
+
+    def clear(self) -> None:
+        self.lib.check(self.lib.lib.ccmi_metrics_processor_clear(self.handle))
 
 
 class ClusterModel:

@@ -281,6 +281,62 @@ extern "C" void ccmi_aggregator_destroy(ccmi_aggregator* a) {
   }
 }
 
+namespace ccmi {
+
+// The host prologue of add_samples: MetricSampleAggregator.addSample over the timestamps alone gives the accepted
+// flags, the roll-outs and the generation. timeMs == nullptr: every sample has the time `sameTimeMs`.
+AggAddPlan aggPlanAddSamples(const ccmi_aggregator& a, const int64_t* timeMs, int64_t sameTimeMs, int64_t n) {
+  AggAddPlan plan;
+  plan.acc.resize((size_t)n);
+  plan.cur = a.current;
+  plan.oldest = a.oldest;
+  plan.gen = a.generation;
+  for (int64_t i = 0; i < n; ++i) {
+    const long long w = windowIndexOf(timeMs ? timeMs[i] : sameTimeMs, a.cfg.window_ms);
+    if (w < plan.oldest) {
+      plan.acc[(size_t)i] = 0;
+      continue;
+    }
+    bool rolled = false;
+    if (plan.cur < w) {  // maybeRollOutNewWindow
+      const long long prevOldest = plan.oldest;
+      plan.oldest = std::max<long long>(1, w - a.cfg.num_windows);
+      const long long numReset = std::min<long long>(a.L(), plan.oldest - prevOldest);
+      if (numReset > 0) plan.events.push_back(ccmi::AggRollEvent{i, plan.oldest, prevOldest, (int32_t)numReset, 0});
+      plan.cur = w;
+      rolled = true;
+    }
+    if (rolled || w != plan.cur) plan.gen++;
+    plan.acc[(size_t)i] = 1;
+    plan.numAccepted++;
+  }
+  return plan;
+}
+
+void AggAddScratch::layout(Carver& c, size_t n, size_t E, size_t numEvents) {
+  c.take(acc, n);
+  c.take(ord, n);
+  c.take(run, E + 1);
+  c.take(cur, E);
+  c.take(ev, numEvents);
+}
+
+// The device body of add_samples over samples that are on the device already; synchronises and commits the plan.
+void aggAddSamplesOnDevice(ccmi_aggregator& a, const AggAddPlan& plan, const AggAddScratch& s, const int32_t* dEntity,
+                           const int64_t* dTime, const double* dValues, int64_t n) {
+  a.up(s.acc, plan.acc.data(), (size_t)n);
+  a.up(s.ev, plan.events.data(), sizeof(ccmi::AggRollEvent) * plan.events.size());
+  ccmi::aggLaunchAddSamples(a.T, dEntity, dTime, dValues, s.acc, n, s.ev, (int)plan.events.size(), a.oldest,
+                            a.cfg.window_ms, s.run, s.cur, s.ord, a.st);
+  hipCheck(hipGetLastError(), "add_samples launch");
+  a.sync();
+  a.current = plan.cur;
+  a.oldest = plan.oldest;
+  a.generation = plan.gen;
+}
+
+}  // namespace ccmi
+
 extern "C" ccmi_status ccmi_aggregator_add_samples(ccmi_aggregator* a, const int32_t* entity, const int64_t* time_ms,
                                                    const double* values, int64_t n, uint8_t* accepted,
                                                    int64_t* num_accepted) {
@@ -295,62 +351,25 @@ extern "C" ccmi_status ccmi_aggregator_add_samples(ccmi_aggregator* a, const int
       if (entity[i] < 0 || entity[i] >= a->cfg.num_entities) throw std::invalid_argument("entity id out of range");
       if (time_ms[i] < 0) throw std::invalid_argument("negative sample time");
     }
-    // MetricSampleAggregator.addSample over the timestamps: the accepted flags, the roll-outs, the generation
-    std::vector<uint8_t> acc((size_t)n);
-    std::vector<ccmi::AggRollEvent> events;
-    long long cur = a->current, oldest = a->oldest, gen = a->generation;
-    int64_t nAcc = 0;
-    for (int64_t i = 0; i < n; ++i) {
-      const long long w = windowIndexOf(time_ms[i], a->cfg.window_ms);
-      if (w < oldest) {
-        acc[(size_t)i] = 0;
-        continue;
-      }
-      bool rolled = false;
-      if (cur < w) {  // maybeRollOutNewWindow
-        const long long prevOldest = oldest;
-        oldest = std::max<long long>(1, w - a->cfg.num_windows);
-        const long long numReset = std::min<long long>(a->L(), oldest - prevOldest);
-        if (numReset > 0) events.push_back(ccmi::AggRollEvent{i, oldest, prevOldest, (int32_t)numReset, 0});
-        cur = w;
-        rolled = true;
-      }
-      if (rolled || w != cur) gen++;
-      acc[(size_t)i] = 1;
-      nAcc++;
-    }
+    const ccmi::AggAddPlan plan = ccmi::aggPlanAddSamples(*a, time_ms, 0, n);
     const ccmi::DeviceGuard dg(a->device);
     const size_t E = (size_t)a->cfg.num_entities, M = (size_t)a->cfg.num_metrics, N = (size_t)n;
     int32_t* dEnt;
     int64_t* dTime;
     double* dVal;
-    uint8_t* dAcc;
-    uint32_t *dOrd, *dRun, *dCur;
-    ccmi::AggRollEvent* dEv;
+    ccmi::AggAddScratch scratch;
     ccmi::carve(a->batch, [&](Carver& c) {
       c.take(dEnt, N);
       c.take(dTime, N);
       c.take(dVal, N * M);
-      c.take(dAcc, N);
-      c.take(dOrd, N);
-      c.take(dRun, E + 1);
-      c.take(dCur, E);
-      c.take(dEv, events.size());
+      scratch.layout(c, N, E, plan.events.size());
     });
     a->up(dEnt, entity, 4 * N);
     a->up(dTime, time_ms, 8 * N);
     a->up(dVal, values, 8 * N * M);
-    a->up(dAcc, acc.data(), N);
-    a->up(dEv, events.data(), sizeof(ccmi::AggRollEvent) * events.size());
-    ccmi::aggLaunchAddSamples(a->T, dEnt, dTime, dVal, dAcc, n, dEv, (int)events.size(), a->oldest, a->cfg.window_ms,
-                              dRun, dCur, dOrd, a->st);
-    hipCheck(hipGetLastError(), "add_samples launch");
-    a->sync();
-    a->current = cur;
-    a->oldest = oldest;
-    a->generation = gen;
-    if (accepted) std::memcpy(accepted, acc.data(), N);
-    if (num_accepted) *num_accepted = nAcc;
+    ccmi::aggAddSamplesOnDevice(*a, plan, scratch, dEnt, dTime, dVal, n);
+    if (accepted) std::memcpy(accepted, plan.acc.data(), N);
+    if (num_accepted) *num_accepted = plan.numAccepted;
     return CCMI_OK;
   });
 }

@@ -73,6 +73,24 @@ struct AggDeviceRows {
   uint8_t *extrapolations = nullptr, *invalid = nullptr;
 };
 
+// ccmi_aggregator_add_samples in two steps, so that samples a kernel left on the device (K20's process_into) take the
+// same path as a host batch: the host prologue over the timestamps, then the device body over device pointers.
+struct AggAddPlan {
+  std::vector<uint8_t> acc;          // accepted flag per sample
+  std::vector<AggRollEvent> events;  // the roll-outs, by sample position
+  long long cur = 0, oldest = 0, gen = 0;  // the aggregator's counters after the batch
+  int64_t numAccepted = 0;
+};
+struct AggAddScratch {  // pieces of a.batch
+  uint8_t* acc = nullptr;
+  uint32_t *ord = nullptr, *run = nullptr, *cur = nullptr;
+  AggRollEvent* ev = nullptr;
+  void layout(Carver& c, size_t n, size_t E, size_t numEvents);
+};
+AggAddPlan aggPlanAddSamples(const ccmi_aggregator& a, const int64_t* timeMs, int64_t sameTimeMs, int64_t n);
+void aggAddSamplesOnDevice(ccmi_aggregator& a, const AggAddPlan& plan, const AggAddScratch& s, const int32_t* dEntity,
+                           const int64_t* dTime, const double* dValues, int64_t n);
+
 // checkOptions of the aggregator's calls: std::invalid_argument for a null or malformed options struct
 void aggCheckOptions(const ccmi_aggregation_options* o);
 // ccmi_aggregator_aggregate up to validateCompleteness: fills `out`; false when out->failure is set (no rows).

@@ -1349,6 +1349,115 @@ typedef struct ccmi_host_cross_counters {
 } ccmi_host_cross_counters;
 ccmi_status ccmi_host_cross_perf(const ccmi_session* s, ccmi_host_cross_counters* out);
 
+/*
+ * ccmi_metrics_processor_*, additive at ABI v13: the capability flag is the presence of the symbols.
+ * CruiseControlMetricsProcessor (monitor/sampling/CruiseControlMetricsProcessor.java with BrokerLoad, RawMetricsHolder
+ * and SamplingUtils) on the device (K20): one sampling round's raw CruiseControlMetric records in, the partition and
+ * broker metric samples out, as the rows ccmi_aggregator_add_samples takes. The consumer, the serde and the sample
+ * stores stay with the caller.
+ *
+ * add_metrics appends a batch in arrival order (addMetric for each record). `type` is the RawMetricType id (0..62);
+ * topic is an index into the batch's topic_names (the names as the reporter wrote them, dots already replaced), -1 for
+ * a broker-scope type; partition is -1 unless the type is PARTITION_SIZE. The records stay on the device.
+ *
+ * process(cluster, nodes, interested, sampling_mode, out) is process(Cluster, partitions, SamplingMode):
+ *   cluster : the partitions (leader_broker_id, replica ranges, topic names with their dots); entity e = partition e.
+ *   nodes   : Cluster.nodes() and, per node, what the BrokerCapacityConfigResolver gives for its CPU cores (NaN:
+ *             nothing). The cache of cores follows updateCachedNumCoresByBroker: filled only for a broker that sent a
+ *             metric and is a node, a NaN is not cached, a cached value survives clear and a later NaN.
+ *   out     : partition samples compacted in ascending partition index (partition_entity[k], partition_values[k][9] in
+ *             KafkaMetricDef.commonMetricDef() id order) and broker samples in node order (broker_node[k] = index into
+ *             nodes, broker_values[k][56] in brokerMetricDef() id order, broker_version[k]); both kinds close at
+ *             max_metric_timestamp. num_* are the full counts, the first *_capacity rows are written.
+ *             partition_skip[P] (nullable): 0 built or not interested, 1 no leader, 2 no broker load or no
+ *             BROKER_CPU_UTIL, 3 no cached cores, 4 the topic has no partition size on the leader, 5 no partition size,
+ *             6 a broker holder of the CPU estimate is missing (the reference throws), 7 the estimate is null, 8 the
+ *             leader is not a node. broker_skip[num_nodes] (nullable): 0 built, 1 no broker load, 2 the minimum
+ *             required metrics are not available, 3 a type of either version is not available.
+ *             skipped_by_node[num_nodes + 1] (nullable): skipped partitions by leader, the last slot is
+ *             UNRECOGNIZED_BROKER_ID (codes 1, 6 and 8). Records of a broker that is not a node take no part and are
+ *             counted in num_dropped_records, so a partition led by such a broker is code 8.
+ *             num_hash_fallback_brokers: nodes whose topic set or partition map would resize early or build a tree bin
+ *             in the JVM; their iteration order came from the host's HashMap emulation (engine/broker_load.h).
+ * The double sums of the reference (an AVG holder in arrival order, the seven ALL_TOPIC_* sums in the iteration order
+ * of a HashSet<String>, diskUsage() in that of a HashMap<TopicPartition, ...>) are added in those orders.
+ * After a process or a process_into, add_metrics and both process calls return CCMI_E_STATE until clear: the reference's second process would see
+ * the holders the first one overwrote. clear forgets the records and max_metric_timestamp, not the cached cores.
+ *
+ * Errors, CCMI_E_INVALID with the text in ccmi_last_error: a NULL argument that is not marked nullable; a type above
+ * 62; a topic or partition index that does not fit the type's scope (or a partition number above 262142); a negative
+ * time; duplicate names in a batch's topic table; duplicate node ids; more than 262143 nodes or 4194302 topics; a
+ * capacity < 0 or a NULL output array with a capacity > 0; an unknown sampling mode. CCMI_E_DEVICE for a device failure.
+ * On an error of add_metrics nothing was added.
+ */
+typedef struct ccmi_metrics_processor ccmi_metrics_processor;
+typedef struct ccmi_metrics_processor_config { /* the static CPU model's weights (ModelParameters) */
+  double cpu_weight_of_leader_bytes_in_rate;   /* 0.7 */
+  double cpu_weight_of_leader_bytes_out_rate;  /* 0.15 */
+  double cpu_weight_of_follower_bytes_in_rate; /* 0.15 */
+  int64_t reserved;
+} ccmi_metrics_processor_config;
+typedef struct ccmi_raw_metrics {
+  int64_t n;
+  int32_t num_topics, reserved;
+  const char* const* topic_names; /* [num_topics] */
+  const uint8_t* type;            /* [n] */
+  const int32_t* broker_id;       /* [n] */
+  const int64_t* time_ms;         /* [n] */
+  const double* value;            /* [n] */
+  const int32_t* topic;           /* [n] */
+  const int32_t* partition;       /* [n] */
+} ccmi_raw_metrics;
+typedef struct ccmi_cluster_nodes {
+  int32_t num_nodes, reserved;
+  const int32_t* broker_id; /* [num_nodes] */
+  const double* num_cores;  /* [num_nodes]; NaN = the resolver gave nothing */
+} ccmi_cluster_nodes;
+typedef enum ccmi_sampling_mode {
+  CCMI_SAMPLING_ALL = 0,
+  CCMI_SAMPLING_BROKER_METRICS_ONLY = 1,
+  CCMI_SAMPLING_PARTITION_METRICS_ONLY = 2,
+  CCMI_SAMPLING_ONGOING_EXECUTION = 3
+} ccmi_sampling_mode;
+typedef struct ccmi_processed_samples {
+  int64_t max_metric_timestamp;
+  int64_t partition_capacity, num_partition_samples;
+  int32_t* partition_entity; /* [partition_capacity] */
+  double* partition_values;  /* [partition_capacity][9] */
+  int64_t broker_capacity, num_broker_samples;
+  int32_t* broker_node;      /* [broker_capacity] */
+  double* broker_values;     /* [broker_capacity][56] */
+  int8_t* broker_version;    /* [broker_capacity] */
+  uint8_t* partition_skip;   /* nullable [P] */
+  uint8_t* broker_skip;      /* nullable [num_nodes] */
+  int32_t* skipped_by_node;  /* nullable [num_nodes + 1] */
+  int32_t num_skipped_brokers, num_hash_fallback_brokers;
+  int64_t num_dropped_records;
+} ccmi_processed_samples;
+ccmi_status ccmi_metrics_processor_create(int32_t device_ordinal,
+                                          const ccmi_metrics_processor_config* config /* nullable: the defaults */,
+                                          ccmi_metrics_processor** out);
+void ccmi_metrics_processor_destroy(ccmi_metrics_processor* p);
+ccmi_status ccmi_metrics_processor_add_metrics(ccmi_metrics_processor* p, const ccmi_raw_metrics* batch);
+ccmi_status ccmi_metrics_processor_process(ccmi_metrics_processor* p, const ccmi_partition_topology* cluster,
+                                           const ccmi_cluster_nodes* nodes, const uint8_t* interested /* nullable [P] */,
+                                           int32_t sampling_mode, ccmi_processed_samples* out);
+/* process, with the rows fed to the aggregators instead of returned: both end in exactly the state that process
+ * followed by ccmi_aggregator_add_samples(entity, max_metric_timestamp, values) gives them, and no row crosses to the
+ * host. The partition aggregator needs E = num_partitions and M = 9, the broker aggregator E = num_nodes (entity = node
+ * index) and M = 56, both on the processor's device (CCMI_E_INVALID otherwise, before anything changes). `out` gets the
+ * counts and the skip tables; its row arrays and capacities are not read. KafkaPartitionMetricSampleAggregator's own
+ * isValid filtering is the caller's. */
+ccmi_status ccmi_metrics_processor_process_into(ccmi_metrics_processor* p, const ccmi_partition_topology* cluster,
+                                                const ccmi_cluster_nodes* nodes,
+                                                const uint8_t* interested /* nullable [P] */, int32_t sampling_mode,
+                                                ccmi_aggregator* partition_aggregator /* nullable */,
+                                                ccmi_aggregator* broker_aggregator /* nullable */,
+                                                ccmi_processed_samples* out);
+ccmi_status ccmi_metrics_processor_cached_num_cores(ccmi_metrics_processor* p, int32_t broker_id,
+                                                    double* out /* NaN = not cached */);
+ccmi_status ccmi_metrics_processor_clear(ccmi_metrics_processor* p);
+
 #ifdef __cplusplus
 }
 #endif
